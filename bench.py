@@ -1,8 +1,18 @@
 """bench.py — denoised latent frames / second of the SVI rolling-window hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c1] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c1] [--dump-outputs DIR] [--full [--no-cpu-baseline]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+
+A plain run does what the headline needs and nothing else: set up, W warm-up steps, the K timed steps, the VAE decode of the
+finished latents (part of `value`), `--dump-outputs` if given, the JSON line.  `--full` adds everything else the line can carry:
+the budget plan (`--budget-s`), the eager instrumented steps behind the timed region (`roofline`, `roofline_all`,
+`kernel_ms_per_step`, `config.attention_second_pass`), the two timed complete clips, the vendor yardstick and the CPU baseline.
+In a plain run those keys are null.
+
+`--dump-outputs DIR` (rank 0) writes what the timed path left after its last step, after the timed region: `latents.npy` (the
+denoised latents [1, 16, T, H, W], float32 from bf16) and `video.npy` (the VAE decode of the latents as they stand at the decode,
+float32; above 4 Mi elements a fixed sample: the elements at `video_sample_index(n)` of the flattened video, seed 0).
 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment launches its own N ranks (it re-executes itself under
 torch.distributed.run on 127.0.0.1, one rank per GPU, RCCL); it refuses — one line on stderr, non-zero exit — when fewer than N GPUs
@@ -30,7 +40,7 @@ cross-attention kernel), `--budget-s S` (wall-clock budget counted from process 
 printed after the warm-up), `--rccl-probe` (N = 1 with a live one-rank RCCL communicator), `--fp8-all` (opt-in: every token-side GEMM and QK^T on MX fp8), and beside an
 RCCL communicator the step graph is tried behind a guard and voted on (`config.hip_graph`, `config.hip_graph_note`).
 
-Extra objects on the JSON line:
+Extra objects on the JSON line (--full; null in a plain run):
   roofline      dominant kernel = self-attention flash kernel: algorithmic 4*L^2*D FLOP per launch divided by
                 its mean launch time measured with HIP events on the launch stream — inside the timed region with --no-graph; with
                 the hipGraph (default) over eager steps of the same loop run directly behind it (a replay cannot carry event pairs).
@@ -80,6 +90,31 @@ PEAK_BF16_TFLOPS = 2500.0      # MI355X dense bf16 MFMA peak (MI355X_MICROARCH.m
 
 def L_TOKENS(T: int, H: int, W: int) -> int:
     return T * (H // 2) * (W // 2)
+
+
+DUMP_SAMPLE = 1 << 22      # --dump-outputs: arrays above this many elements are written as a fixed sample of this many
+
+
+def video_sample_index(n: int) -> torch.Tensor:
+    """The fixed, seeded sample of a flattened array of n elements that --dump-outputs writes: one element drawn from each of DUMP_SAMPLE equal
+    strata of the index range (sorted int64 indices)."""
+    if n <= DUMP_SAMPLE:
+        return torch.arange(n)
+    m = DUMP_SAMPLE
+    lo = torch.arange(m, dtype=torch.int64) * n // m
+    width = torch.arange(1, m + 1, dtype=torch.int64) * n // m - lo
+    return lo + (torch.rand(m, generator=torch.Generator().manual_seed(0), dtype=torch.float64) * width).long()
+
+
+def dump_outputs(out_dir: str, lat: torch.Tensor, vid) -> None:
+    """--dump-outputs: the latents after the last timed step and the decoded video (or its fixed sample), float32 .npy files."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "latents.npy"), lat.float().cpu().numpy())
+    if vid is not None:
+        flat = vid.detach().float().reshape(-1)
+        v = vid.float().cpu() if flat.numel() <= DUMP_SAMPLE else flat[video_sample_index(flat.numel()).to(flat.device)].cpu()
+        np.save(os.path.join(out_dir, "video.npy"), v.numpy())
 
 
 def vendor_yardstick(timeout_s: int = 240):
@@ -340,7 +375,12 @@ def main() -> None:
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default="c2", choices=list(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="besides the headline: the budget plan, roofline / per-kernel figures from instrumented eager steps, the two timed "
+                    "complete clips, the vendor yardstick and the CPU baseline (the --no-* switches below drop single parts).  Off: only what `value` and "
+                    "`ms_per_step` need")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the latents after the last timed step and the decoded video (a fixed sample "
+                    "above 4 Mi elements) to DIR/<name>.npy, float32; rank 0")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline child")
     ap.add_argument("--no-vae", action="store_true")
     ap.add_argument("--cfg-pair", action="store_true", help="SURVEY 8e-2: ranks (2p,2p+1) split the cond/uncond forwards of clip p "
                     "(one 4.2 MB all-gather per step); needs an even --gpus. Default is one clip per rank.")
@@ -366,7 +406,7 @@ def main() -> None:
     ap.add_argument("--transport", default="nccl", choices=["nccl", "gloo"], help="process-group backend of a multi-rank run.  nccl (= RCCL over xGMI): one GPU per "
                     "rank, the measured configuration.  gloo: the exchanges go through the host and the ranks may SHARE a device (rank r -> device r mod visible) — a "
                     "probe that drives the whole multi-rank code path (shard, exchange, max-over-ranks, aggregation) on a one-GPU box; its line says so and is not a scaling figure")
-    ap.add_argument("--no-full-clip", dest="full_clip", action="store_false", help="skip the two COMPLETE clips timed behind the K-step region (the metric as defined, "
+    ap.add_argument("--no-full-clip", dest="full_clip", action="store_false", help="with --full: skip the two COMPLETE clips timed behind the K-step region (the metric as defined, "
                     "not its extrapolation): clip 1 = first eager step + hipGraph capture + context-cache fill + the remaining replays + VAE decode + 8-bit frames; clip 2 = the "
                     "same stream's next clip on the resident loop (replays only) -> config.full_clip_s / value_full_clip / full_clip_steady_s")
     ap.add_argument("--window", type=int, default=0, metavar="K", help="BASELINE configs[2] as a workload: a rolling window of K clips (seed = k x 42, prompts cycled, "
@@ -380,10 +420,10 @@ def main() -> None:
     ap.add_argument("--prompt-tokens", type=int, default=64, metavar="N", help="valid (non-padded) tokens of the positive prompt (the negative prompt gets N // 2): the context's "
                     "remaining rows are the prompter's zero padding = one more distinct key.  Default 64 / 32; beyond 127 valid tokens the cross-attention leaves "
                     "flash_cross_resident_kernel (keys resident in LDS) for the streaming kernel")
-    ap.add_argument("--budget-s", type=float, default=600.0, metavar="S", help="wall-clock budget of this invocation, counted from process start.  The K timed steps are never "
+    ap.add_argument("--budget-s", type=float, default=600.0, metavar="S", help="with --full: wall-clock budget of this invocation, counted from process start.  The K timed steps are never "
                     "trimmed; what is optional around them is: the two timed complete clips go when they would not fit, then the vendor yardstick.  The expected total is "
                     "printed on stderr after the warm-up and reported as config.wall_s_expected beside config.wall_s")
-    ap.add_argument("--no-vendor", action="store_true", help="skip the vendor yardstick child (tools/yardstick.py: hipBLASLt / SDPA on the step's six hot shapes, same box, same "
+    ap.add_argument("--no-vendor", action="store_true", help="with --full: skip the vendor yardstick child (tools/yardstick.py: hipBLASLt / SDPA on the step's six hot shapes, same box, same "
                     "job; N = 1, c2 only) whose figures stand beside every family of roofline_all as `vendor`")
     ap.add_argument("--rccl-probe", action="store_true", help="N = 1 only: create the RCCL process group anyway (a one-rank communicator) so that the barrier, the tail all-gather and "
                     "the MAX-reduce of the timed region go through RCCL and the step's hipGraph is captured beside a live communicator — the part of the multi-GPU path a "
@@ -402,6 +442,8 @@ def main() -> None:
         args.fp8_mfma = args.fp8_attn = True
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args.gpus, args.launcher_selftest, args.transport))
 
@@ -579,43 +621,47 @@ def main() -> None:
         one_step(i)
     sync()
     hb.mark("warmup-done", f"hip_graph={bool(args.graph)}")
-    # ---- wall-clock plan (--budget-s): what is still ahead, priced with a step time taken now --------------------------------------------------------
-    if dist is not None:
-        dist.barrier()
-    torch.cuda.synchronize()
-    t_probe = time.perf_counter()
-    one_step(args.warmup)
-    torch.cuda.synchronize()
-    step_est = time.perf_counter() - t_probe
-    want_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline
-    want_vendor = rank == 0 and world == 1 and not args.no_vendor and args.workload == "c2" and not args.seq_parallel
-    plan = {"timed_steps": args.steps * step_est, "eager_profile_steps": 8 * step_est * 1.05, "vae": 0.0 if args.no_vae else 6.0,
-            "full_clips": 2.0 * (spc * step_est + 1.5) + 3.0 if (args.full_clip and not args.no_vae and not wl.get("pose")) else 0.0,
-            "window": (args.window * (2 if args.window_ab else 1) / max(world, 1)) * (spc * step_est + 1.5) if args.window > 0 else 0.0,
-            "cpu_baseline": 110.0 if want_cpu else 0.0, "vendor_yardstick": 45.0 if want_vendor else 0.0}
-    used = time.perf_counter() - T_PROCESS_START
-    trimmed = []
-    if args.budget_s > 0:
-        def over():
-            return used + sum(plan.values()) > args.budget_s
-        if over() and plan["full_clips"]:
-            plan["full_clips"] = 0.0
-            args.full_clip = False
-            trimmed.append("full clips")
-        if over() and plan["vendor_yardstick"]:
-            plan["vendor_yardstick"] = 0.0
-            want_vendor = False
-            trimmed.append("vendor yardstick")
-    if dist is not None:            # every rank drops the same parts (the full clips hold collectives): the slowest rank's plan decides
-        tv = torch.tensor([0.0 if args.full_clip else 1.0], device=dev)
-        dist.all_reduce(tv, op=dist.ReduceOp.MAX)
-        if tv.item() > 0 and args.full_clip:
-            args.full_clip = False
-            plan["full_clips"] = 0.0
-            trimmed.append("full clips (another rank's plan)")
-    wall_expected = used + sum(plan.values())
-    print(f"bench.py[rank {rank}/{world}]: {used:.0f} s used, step ~{step_est * 1e3:.0f} ms, expected total ~{wall_expected:.0f} s of --budget-s {args.budget_s:.0f}"
-          + (f" (trimmed: {', '.join(trimmed)})" if trimmed else ""), file=sys.stderr, flush=True)
+    # ---- wall-clock plan (--budget-s): what is still ahead, priced with a step time taken now (--full only: a plain run has nothing optional) -------
+    want_cpu = want_vendor = False
+    trimmed, wall_expected = [], None
+    if not args.full:
+        args.full_clip = False
+    else:
+        if dist is not None:
+            dist.barrier()
+        torch.cuda.synchronize()
+        t_probe = time.perf_counter()
+        one_step(args.warmup)
+        torch.cuda.synchronize()
+        step_est = time.perf_counter() - t_probe
+        want_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline
+        want_vendor = rank == 0 and world == 1 and not args.no_vendor and args.workload == "c2" and not args.seq_parallel
+        plan = {"timed_steps": args.steps * step_est, "eager_profile_steps": 8 * step_est * 1.05, "vae": 0.0 if args.no_vae else 6.0,
+                "full_clips": 2.0 * (spc * step_est + 1.5) + 3.0 if (args.full_clip and not args.no_vae and not wl.get("pose")) else 0.0,
+                "window": (args.window * (2 if args.window_ab else 1) / max(world, 1)) * (spc * step_est + 1.5) if args.window > 0 else 0.0,
+                "cpu_baseline": 110.0 if want_cpu else 0.0, "vendor_yardstick": 45.0 if want_vendor else 0.0}
+        used = time.perf_counter() - T_PROCESS_START
+        if args.budget_s > 0:
+            def over():
+                return used + sum(plan.values()) > args.budget_s
+            if over() and plan["full_clips"]:
+                plan["full_clips"] = 0.0
+                args.full_clip = False
+                trimmed.append("full clips")
+            if over() and plan["vendor_yardstick"]:
+                plan["vendor_yardstick"] = 0.0
+                want_vendor = False
+                trimmed.append("vendor yardstick")
+        if dist is not None:            # every rank drops the same parts (the full clips hold collectives): the slowest rank's plan decides
+            tv = torch.tensor([0.0 if args.full_clip else 1.0], device=dev)
+            dist.all_reduce(tv, op=dist.ReduceOp.MAX)
+            if tv.item() > 0 and args.full_clip:
+                args.full_clip = False
+                plan["full_clips"] = 0.0
+                trimmed.append("full clips (another rank's plan)")
+        wall_expected = used + sum(plan.values())
+        print(f"bench.py[rank {rank}/{world}]: {used:.0f} s used, step ~{step_est * 1e3:.0f} ms, expected total ~{wall_expected:.0f} s of --budget-s {args.budget_s:.0f}"
+              + (f" (trimmed: {', '.join(trimmed)})" if trimmed else ""), file=sys.stderr, flush=True)
     # Over the timed region only the dominant kernel is bracketed by HIP events (`roofline`): every event record is a packet between two
     # kernels of the stream it measures, and the ~1440 records of a fully instrumented C2 step cost that step about 1 % (profiles/r3m_prof_events_ab.txt).
     # The breakdown over all kernel families (`roofline_all`, `kernel_ms_per_step`) comes from `prof_steps` fully instrumented steps run
@@ -636,31 +682,33 @@ def main() -> None:
     prof_timed = _lib.prof_summary()
     _lib.prof_enable(False)
     _lib.prof_select(None)
+    lat_out = lat.clone() if args.dump_outputs and rank == 0 else None      # --dump-outputs: the timed path's result, before any step behind it
     prof, prof_steps, roof_steps = prof_timed, args.steps, args.steps
     roof_source = "HIP events on the launch stream over the timed region"
-    if args.graph:
-        # a replayed hipGraph cannot carry per-kernel event pairs: the dominant kernel is timed over `roof_steps` EAGER steps of the same loop
-        # state directly behind the timed region (only that kernel bracketed: the step is otherwise undisturbed), then every family
-        loop.drop_graph()
-        roof_steps = max(1, min(4, args.steps))
-        _lib.prof_select(["flash_self"])
-        _lib.prof_enable(True)
-        for i in range(roof_steps):
-            one_step(args.warmup + args.steps + i, eager_loop)
-        torch.cuda.synchronize()
-        prof_timed = _lib.prof_summary()
-        _lib.prof_enable(False)
-        _lib.prof_select(None)
-        roof_source = (f"HIP events on the launch stream over {roof_steps} eager steps run directly behind the timed region (the timed region replays one hipGraph per "
-                       "step, inside which no event pair can be taken; same kernels, same operands)")
-    if not args.profile_all or args.graph:
-        prof_steps = max(1, min(4, args.steps))
-        _lib.prof_enable(True)
-        for i in range(prof_steps):
-            one_step(args.warmup + args.steps + roof_steps + i, eager_loop)
-        torch.cuda.synchronize()
-        prof = _lib.prof_summary()
-        _lib.prof_enable(False)
+    if args.full:
+        if args.graph:
+            # a replayed hipGraph cannot carry per-kernel event pairs: the dominant kernel is timed over `roof_steps` EAGER steps of the same loop
+            # state directly behind the timed region (only that kernel bracketed: the step is otherwise undisturbed), then every family
+            loop.drop_graph()
+            roof_steps = max(1, min(4, args.steps))
+            _lib.prof_select(["flash_self"])
+            _lib.prof_enable(True)
+            for i in range(roof_steps):
+                one_step(args.warmup + args.steps + i, eager_loop)
+            torch.cuda.synchronize()
+            prof_timed = _lib.prof_summary()
+            _lib.prof_enable(False)
+            _lib.prof_select(None)
+            roof_source = (f"HIP events on the launch stream over {roof_steps} eager steps run directly behind the timed region (the timed region replays one hipGraph per "
+                           "step, inside which no event pair can be taken; same kernels, same operands)")
+        if not args.profile_all or args.graph:
+            prof_steps = max(1, min(4, args.steps))
+            _lib.prof_enable(True)
+            for i in range(prof_steps):
+                one_step(args.warmup + args.steps + roof_steps + i, eager_loop)
+            torch.cuda.synchronize()
+            prof = _lib.prof_summary()
+            _lib.prof_enable(False)
     if dist is not None:
         tmax = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -669,7 +717,7 @@ def main() -> None:
     # the last self-attention launch of the eager steps above: how many of its workgroups the optimistic pass handed to the second pass (0 on every
     # random-init forward measured so far; --attn-gain makes the logits peaky)
     second_pass = None
-    if L_TOKENS(T, H, W) >= 2048 and not sp:
+    if args.full and L_TOKENS(T, H, W) >= 2048 and not sp:
         import ctypes as _C
         fa, fb = _C.c_int32(), _C.c_int32()
         if _lib.lib().svi_attention_last_flagged(_lib.current_stream(), _C.byref(fa), _C.byref(fb)) == 0 and fb.value > 0:
@@ -679,7 +727,7 @@ def main() -> None:
 
     # VAE decode of the finished clip (fp32, as pipelines/svi_video.py:385-389), timed once on the same stream; for the I2V
     # model also the per-clip conditioning encode y = mask | VAE.encode([motion frame | zeros]) (svi_video.py:291-350)
-    vae_ms, enc_ms = None, None
+    vae_ms, enc_ms, vid = None, None, None
     if not args.no_vae:
         from svi_hip.vae import WanVideoVAE, device_vae_weights
         vae = WanVideoVAE.from_state_dict(device_vae_weights(0, dev))
@@ -711,6 +759,9 @@ def main() -> None:
         vae_ms = float(red[0].item()) if vae_ms is not None else None
         enc_ms = float(red[2].item()) if enc_ms is not None else None
         finite = red[1].item() == 0.0
+    if lat_out is not None:
+        dump_outputs(args.dump_outputs, lat_out, vid)
+        del lat_out
     # ---- the metric as DEFINED — (clips x 21 latent frames) / wall time — timed, not extrapolated ----------------------------------
     def timed_clip(lp, k: int) -> dict:
         """One complete clip on loop `lp` the way the rolling window runs it: seeded noise -> [I2V: conditioning encode] -> DenoiseLoop.sample (all
@@ -843,7 +894,7 @@ def main() -> None:
     fl = prof_timed.get("flash_self", {"count": 0, "ms": 0.0})          # the dominant kernel: events over the timed region itself
     fp8_attn_on = args.fp8_attn or os.environ.get("SVI_ATTN_QK8", "0") not in ("", "0")
     roof = None
-    if fl["count"]:
+    if args.full and fl["count"]:
         per_launch_ms = fl["ms"] / fl["count"]
         alg = 4.0 * L * L * D / (dist.get_world_size(sp_group) if sp else 1)      # a sequence-parallel rank attends with heads / S
         ach = alg / (per_launch_ms * 1e-3) / 1e12
@@ -943,7 +994,7 @@ def main() -> None:
                                   "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s (f16 MFMA equivalent)", "frac": round(3 * vflop / (vae_ms * 1e-3) / 1e12 / PEAK_BF16_TFLOPS, 4),
                                   "fp32_equivalent_tflops": round(vflop / (vae_ms * 1e-3) / 1e12, 1)}
     roof_all = {k: v for k, v in roof_all.items() if v is not None}
-    if args.workload == "c2" and not sp:
+    if args.full and args.workload == "c2" and not sp:
         pm = pmc_summaries()
         for fam_name, key in (("flash_self", "flash"), ("gemm_ffn1", "gemm_ffn1"), ("gemm_ffn2", "gemm_ffn2"), ("flash_cross", "flash_cross"), ("vae_decode", "vae_conv")):
             if fam_name in roof_all and pm.get(key):
@@ -972,7 +1023,7 @@ def main() -> None:
                    f"whole streams, so this figure is an upper bound for a single I2V stream's multi-GPU throughput", "value_is": value_src, **full_cfg, "window": window, "step": (f"1 scheduler step = cond+uncond DiT forward ({NL} blocks each; the pose condition enters the conditional branch only, so the two "
                                                     "forwards share nothing) + CFG + Euler") if wl.get("pose") else
                    f"1 scheduler step = cond+uncond DiT forward ({NL} blocks each; block 0's self-attention, whose operands are identical in both, is computed once — outputs bit-identical to two separate forwards) + CFG + Euler",
-                   "cfg_pair_stacked": bool(stacked),       # behind the shared block-0 self-attention, every row-local kernel runs once over both branches' rows (2 L); bit-identical
+                   "cfg_pair_stacked": bool(stacked) if args.full else None,       # behind the shared block-0 self-attention, every row-local kernel runs once over both branches' rows (2 L); bit-identical
                    "steps_per_clip": spc, "tokens": L, "clips_per_gpu": round(units / world, 4),
                    "sp_cfg_pair": getattr(loop, "last_sp_form", None),      # sequence-parallel steps: "stacked pair" = both CFG branches stacked on every rank's rows
                    "parallelism": (f"one clip: {'cfg-pair x ' if pair else ''}sequence-parallel over {world} ranks" +
@@ -1000,15 +1051,16 @@ def main() -> None:
                    "float8_e4m3fn storage, cast to bf16 at bind (reference FP8 mode)" if args.fp8_storage else "bf16",
                    "outputs_finite": finite},
         "roofline": roof,
-        "roofline_all": roof_all,
-        "kernel_ms_per_step": {k: round(v["ms"] / prof_steps, 3) for k, v in prof.items()},
-        "kernel_ms_source": ("HIP events of every tagged kernel family inside the timed region" if (args.profile_all and not args.graph) else
+        "roofline_all": roof_all if args.full else None,
+        "kernel_ms_per_step": {k: round(v["ms"] / prof_steps, 3) for k, v in prof.items()} if args.full else None,
+        "kernel_ms_source": None if not args.full else ("HIP events of every tagged kernel family inside the timed region" if (args.profile_all and not args.graph) else
                              f"{prof_steps} fully instrumented eager steps behind the timed region" + (" (which replays one hipGraph per step)" if args.graph else
                              " (inside it only the dominant kernel is bracketed by events; `roofline` is from those)")),
     }
     line["config"].update({"attention_second_pass": second_pass, "prompt_tokens": [args.prompt_tokens, max(1, args.prompt_tokens // 2)],
                            "hip_graph_note": graph_note, "rccl_probe": bool(args.rccl_probe) or None,
-                           "budget_s": args.budget_s, "budget_trimmed": trimmed or None, "wall_s_expected": round(wall_expected, 1)})
+                           "budget_s": args.budget_s, "budget_trimmed": trimmed or None,
+                           "wall_s_expected": None if wall_expected is None else round(wall_expected, 1), "full": bool(args.full)})
     if rank == 0 and want_vendor:
         # the vendor libraries on the same shapes, same box, same job (after every timed part of this process; the child has the GPU to itself)
         torch.cuda.synchronize()
@@ -1038,7 +1090,7 @@ def main() -> None:
              "(v transposed by a launch of its own and the softmax scale applied inside the kernel: the DiT's instance needs neither)")
     line["config"]["wall_s"] = round(time.perf_counter() - T_PROCESS_START, 1)
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if want_cpu:
             line["cpu_baseline"] = cpu_baseline()
             line["config"]["wall_s"] = round(time.perf_counter() - T_PROCESS_START, 1)
         else:

@@ -60,7 +60,7 @@ def test_rolling_window_and_full_clips_two_ranks():
     8-bit frames, the frames all-gathered and the window stitched (every clip but the last loses its motion frame); `value` is the window's frames
     per second of wall clock.  The resident loop captures its step graph once per rank; the A/B against re-capturing per clip gives the same video.
     Beside it the two timed complete clips (config.full_clip_s / full_clip_steady_s)."""
-    line = run(["--gpus", "2", "--window", "3", "--window-ab"], vae=True)
+    line = run(["--gpus", "2", "--window", "3", "--window-ab", "--full"], vae=True)
     common(line, 2)
     w = line["config"]["window"]
     assert w["resident"]["clips"] == 3 and w["resident"]["clips_this_rank"] == 2 and w["resident"]["stitched_frames"] == 16 * 2 + 17
@@ -74,7 +74,7 @@ def test_rolling_window_and_full_clips_two_ranks():
 
 def test_full_clip_single_rank():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, BENCH, "--workload", "c1", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
+    r = subprocess.run([sys.executable, BENCH, "--workload", "c1", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     c = line["config"]
@@ -89,7 +89,7 @@ def test_one_rank_rccl_communicator_beside_the_step_graph():
     the timed region go through it, and the step's hipGraph is captured and replayed beside the live communicator behind the guarded probe step that the
     multi-GPU default uses (VERDICT r5 next #7b).  Either outcome of the guard is legal; the line must say which ran."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, BENCH, "--rccl-probe", "--workload", "c1", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-vae", "--no-vendor"],
+    r = subprocess.run([sys.executable, BENCH, "--rccl-probe", "--workload", "c1", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-vae", "--no-vendor"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -103,7 +103,7 @@ def test_one_rank_rccl_communicator_beside_the_step_graph():
 def test_peaky_attention_and_long_prompt_lines():
     """--attn-gain / --prompt-tokens: the line carries the second-pass census of the last self-attention and the prompt's valid tokens."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, BENCH, "--workload", "c1", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-vae", "--no-full-clip", "--attn-gain", "3",
+    r = subprocess.run([sys.executable, BENCH, "--workload", "c1", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-vae", "--no-full-clip", "--attn-gain", "3",
                         "--prompt-tokens", "200"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -112,3 +112,27 @@ def test_peaky_attention_and_long_prompt_lines():
     assert "keys walked: [201, 101]" in line["roofline_all"]["flash_cross"]["what"]
     # c1 has 1280 tokens: below the long-sequence kernel's threshold, so there is no second pass to count
     assert c["attention_second_pass"] is None
+
+
+def test_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """A plain run (no --full) times the steps and decodes the clip, and nothing else: the per-kernel figures, the timed clips and the CPU baseline
+    are null.  --dump-outputs writes the latents of the last timed step and the decoded video as float32 .npy files; with the same arguments a
+    second run writes the same bits."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    got = []
+    for k in range(2):
+        out = tmp_path / f"run{k}"
+        r = subprocess.run([sys.executable, BENCH, "--workload", "c1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(out)], env=env,
+                           capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
+        line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        c = line["config"]
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and c["outputs_finite"] and c["full"] is False
+        assert line["roofline"] is None and line["roofline_all"] is None and line["kernel_ms_per_step"] is None and line["cpu_baseline"] is None
+        assert "full_clip_s" not in c and "vendor_yardstick" not in line and c["vae_decode_ms"] > 0
+        lat, vid = np.load(out / "latents.npy"), np.load(out / "video.npy")
+        assert lat.dtype == np.float32 and lat.shape == (1, 16, 5, 32, 32) and np.isfinite(lat).all()
+        assert vid.dtype == np.float32 and vid.shape == (1, 3, 17, 256, 256) and np.isfinite(vid).all()
+        got.append((lat, vid))
+    assert np.array_equal(got[0][0], got[1][0]) and np.array_equal(got[0][1], got[1][1])

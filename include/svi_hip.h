@@ -82,7 +82,7 @@ int32_t svi_device_count(void);
  * compute the same result, bit for bit or within the stated parity bounds — and SVI_WS_LIMIT_MB, a budget in MiB beyond which a DiT workspace is refused with
  * SVI_ERR_OOM as if the allocation had failed (callers that share the device; the stacked CFG pair then falls back to its unstacked form, same bits);
  * csrc/svi_common.h SviSwitches) once, at first use; tools that flip them inside one process
- * call this afterwards.  Switches that change results exist only in variant builds (-DSVI_ABLATIONS), never in the product — with ONE documented
+ * call this afterwards.  The product library has no switch that changes results — with ONE documented
  * exception, off by default: SVI_ATTN_QK8=1 selects the opt-in quantised-QK^T attention (every long-sequence attention call quantises Q and K to
  * MX e4m3, one E8M0 scale per 32 channels, and takes QK^T on v_mfma_scale_f32_32x32x64_f8f6f4; softmax and P·V unchanged).  Like svi_dit_ffn_mx8
  * below it is arithmetic the reference never performs — its attention dispatch (models/wan_video_dit.py:116-147) merely accepts a quantised-QK^T

@@ -35,12 +35,7 @@ static SviSwitches parse_switches() {
     s.flash_kernel = env_int("SVI_FLASH_KERNEL", 1, 0);
     if (s.flash_kernel > 2) s.flash_kernel = 0;
     s.gemm_kernel = env_int("SVI_GEMM_KERNEL", 128, 0);
-#ifdef SVI_GEMM_EXPERIMENTS
-    const bool experiment = s.gemm_kernel == 264 || s.gemm_kernel == 265;      // the four-wave tiles of round 6 (variant builds only)
-#else
-    const bool experiment = false;
-#endif
-    if (s.gemm_kernel != 128 && s.gemm_kernel != 192 && s.gemm_kernel != 259 && s.gemm_kernel != 260 && !experiment) {
+    if (s.gemm_kernel != 128 && s.gemm_kernel != 192 && s.gemm_kernel != 259 && s.gemm_kernel != 260) {
         if (s.gemm_kernel != 0)      // 256 / 257 / 258 were kernels of rounds 1-3: an old A/B script must not silently measure "auto" instead
             fprintf(stderr, "libsvi_hip: ignoring SVI_GEMM_KERNEL=%d (kernels: 128, 192, 259 = 256^2 four phases, 260 = 256^2 two phases; 256 / 257 / 258 are retired)\n", s.gemm_kernel);
         s.gemm_kernel = 0;
@@ -67,12 +62,6 @@ static SviSwitches parse_switches() {
     if (s.flash_split > 4) s.flash_split = 4;
     s.ws_limit_mb = env_int("SVI_WS_LIMIT_MB", 1, 0);
     { const char* v = getenv("SVI_T5_BUCKETS"); s.t5_host_buckets = v && strcmp(v, "host") == 0; }
-#ifdef SVI_ABLATIONS
-    s.flash_abl = env_int("SVI_FLASH_ABL", 0, 0);
-    s.gemm_epi_abl = env_int("SVI_GEMM_EPI_ABL", 0, 0);
-    s.vae_abl = env_int("SVI_VAE_ABL", 0, 0);
-    s.flash_assume_prescaled = getenv("SVI_FLASH_ASSUME_PRESCALED") != nullptr;
-#endif
     return s;
 }
 // The parsed switches live behind an atomic pointer: a reload publishes a NEW immutable struct (the old ones are kept — a few hundred bytes per reload, A/B
@@ -354,12 +343,7 @@ extern "C" svi_status svi_attention_fwd(const void* q, const void* k, const void
         const bf16* vi = reinterpret_cast<const bf16*>(v) + (size_t)i * s_kv * D;
         bf16* oi = reinterpret_cast<bf16*>(out) + (size_t)i * s_q * D;
         SVI_TRY(svi_launch_transpose(vi, D, vt, ldvt, s_kv, D, st));
-#ifdef SVI_ABLATIONS       // timing aid of tools/attn_abl.py (results wrong by the scale factor): variant builds only
-        const int prescaled = svi_switches().flash_assume_prescaled;
-#else
-        const int prescaled = 0;
-#endif
-        SVI_TRY(svi_launch_flash(qi, D, ki, D, vt, ldvt, oi, D, s_q, s_kv, n, prescaled, st));
+        SVI_TRY(svi_launch_flash(qi, D, ki, D, vt, ldvt, oi, D, s_q, s_kv, n, 0, st));
     }
     return SVI_OK;
 }

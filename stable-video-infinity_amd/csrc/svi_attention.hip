@@ -579,17 +579,6 @@ __global__ __launch_bounds__(512, 2) void flash_cross_resident_kernel(const bf16
 #define SVI_RESCALE_THR 8.0f
 #define SVI_OPT_HEADROOM 64.0f            // log2 units the optimistic pass's fixed reference sits above the tile-0 row maximum (see the prologue of flash_fwd2_kernel)
 #define SVI_OPT_FLAG_SUM 7.9228163e28f    // 2^96: a row sum at or beyond it (or inf / NaN) sends the workgroup to the second pass
-#ifndef SVI_FLASH_BALANCED
-#define SVI_FLASH_BALANCED 1
-#endif
-#ifndef SVI_FLASH_SHORT_NOP
-#define SVI_FLASH_SHORT_NOP 1
-#endif
-#ifndef SVI_FLASH_DMA_SPLIT
-#define SVI_FLASH_DMA_SPLIT 0     // 1: a statement that issues an LDS-DMA piece hands its fragment read to the next statement (balanced kernel only).
-                                  // Measured (same box, interleaved, profiles/r3e_attn_split_ab.txt): 5.025 ms against 4.981 ms without — the read
-                                  // one statement later costs more than the lighter DMA statement returns.  Kept as a recorded negative result.
-#endif
 
 __device__ __forceinline__ float vmax3(float a, float b, float c) {
     float r;
@@ -673,24 +662,13 @@ __device__ __forceinline__ void qk_mfma(int& tok, f32x16& s, u32x4 kf, int& apin
 #define SVI_EXP1 "v_exp_f32 %[t1], %[x1]\n\t"
 #define SVI_MEXP0 "v_mul_f32 %[t0], %[x0], %[c]\n\tv_exp_f32 %[t0], %[t0]\n\t"
 #define SVI_MEXP1 "v_mul_f32 %[t1], %[x1], %[c]\n\tv_exp_f32 %[t1], %[t1]\n\t"
-#ifndef SVI_FLASH_SUM_DOT2     /* default: fp32 row sums of the unrounded p, one v_add per score */
+// Row sums are fp32 sums of the unrounded p, one v_add per score.  Measured and dropped (code at e21fc0e):
+// summing the PACKED bf16 pair with one v_dot2c_f32_bf16 against (1, 1) took 5.52 ms vs 5.09 ms per launch, and v_pk_add_f32 over register
+// pairs 5.53 ms vs 5.01 ms — on this part a VOP3P instruction in an MFMA shadow costs more than two plain VOP2 adds.
 #define SVI_ADD0 "v_add_f32 %[a0], %[a0], %[t0]\n\t"
 #define SVI_ADD1 "v_add_f32 %[a1], %[a1], %[t1]\n\t"
-#define SVI_DOT ""
 #define SVI_ADDU0 "v_add_f32 %[a0], %[a0], %[u0]\n\t"
-#else
-/* -DSVI_FLASH_SUM_DOT2 (tools/build_variant.py): row sum += lo + hi of the PACKED pair with one v_dot2c_f32_bf16 against bf16 (1, 1),
-   i.e. exp, exp, pack, dot instead of exp, exp, add, add, pack.  Measured on one box, same process order: 5.52 ms vs 5.09 ms per
-   launch — the dot instruction costs far more than the two adds it replaces.  Kept only as a recorded negative result.
-   The same holds for v_pk_add_f32 (pairs of exponentials in aligned register pairs, one packed add per pair, added one
-   statement late): correct, no register copies, and 5.53 ms vs 5.01 ms.  On this part a VOP3P instruction in an MFMA shadow
-   costs more than two plain VOP2 adds; the softmax stays on v_add / v_max3 / v_cvt_pk. */
-#define SVI_ADD0 ""
-#define SVI_ADD1 ""
-#define SVI_DOT "v_dot2c_f32_bf16 %[a1], 0x3f803f80, %[w]\n\t"
-#define SVI_ADDU0 ""
-#endif
-#define SVI_CVT "v_cvt_pk_bf16_f32 %[w], %[t0], %[t1]\n\t" SVI_DOT
+#define SVI_CVT "v_cvt_pk_bf16_f32 %[w], %[t0], %[t1]\n\t"
 #define SVI_MAX3 "v_max3_f32 %[m], %[m], %[y0], %[y1]\n\t"
 #define SVI_DMA_M0 "s_mov_b32 m0, %[m0v]\n\t"        /* in front of the MFMA: the MFMA is the wait state m0 needs */
 #define SVI_DMA "buffer_load_dwordx4 %[vo], %[rs], %[so] offen lds\n\t"
@@ -736,9 +714,9 @@ __device__ __forceinline__ void qk_stmt(int& tok, f32x16& s, u32x4 kf, u32x4 kf2
         else asm volatile(SVI_DMA_M0 SVI_EXP1 SVI_QKN SVI_ADD1 SVI_CVT SVI_DMA SVI_END : SVI_QK_OUT("+v"), [t1] "=&v"(t1), [a1] "+v"(sum1), [w] "=&v"(w) : SVI_QK_IN, [x1] "v"(x1), [t0] "v"(t0), SVI_DMA_IN);
     } else {   // E2, never FIRST, never DMA
         float u0;
-        if constexpr (MULC) asm("v_mul_f32 %[u0], %[x0], %[c]\n\tv_exp_f32 %[u0], %[u0]\n\t" SVI_MEXP1 SVI_QKN SVI_ADDU0 SVI_ADD1 "v_cvt_pk_bf16_f32 %[w], %[u0], %[t1]\n\t" SVI_DOT SVI_END
+        if constexpr (MULC) asm("v_mul_f32 %[u0], %[x0], %[c]\n\tv_exp_f32 %[u0], %[u0]\n\t" SVI_MEXP1 SVI_QKN SVI_ADDU0 SVI_ADD1 "v_cvt_pk_bf16_f32 %[w], %[u0], %[t1]\n\t" SVI_END
                                 : SVI_QK_OUT("+v"), [u0] "=&v"(u0), [t1] "=&v"(t1), [a0] "+v"(sum0), [a1] "+v"(sum1), [w] "=&v"(w) : SVI_QK_IN, [x0] "v"(x0), [x1] "v"(x1), [c] "s"(c));
-        else asm("v_exp_f32 %[u0], %[x0]\n\t" SVI_EXP1 SVI_QKN SVI_ADDU0 SVI_ADD1 "v_cvt_pk_bf16_f32 %[w], %[u0], %[t1]\n\t" SVI_DOT SVI_END
+        else asm("v_exp_f32 %[u0], %[x0]\n\t" SVI_EXP1 SVI_QKN SVI_ADDU0 SVI_ADD1 "v_cvt_pk_bf16_f32 %[w], %[u0], %[t1]\n\t" SVI_END
                  : SVI_QK_OUT("+v"), [u0] "=&v"(u0), [t1] "=&v"(t1), [a0] "+v"(sum0), [a1] "+v"(sum1), [w] "=&v"(w) : SVI_QK_IN, [x0] "v"(x0), [x1] "v"(x1));
     }
 }
@@ -881,14 +859,12 @@ __device__ __forceinline__ void pv_mfma(int& tok, u32x4 vf, u32x4 p, int& apin) 
     asm("v_mfma_f32_32x32x16_bf16 a[%c[o0]:%c[o1]], %[vf], %[p], a[%c[o0]:%c[o1]]"
         : [tok] "+v"(tok), [ap] "+v"(apin) : [vf] "v"(vf), [p] "v"(p), [o0] "n"(R), [o1] "n"(R + 15));
 }
-// ABL: timing-only ablation mask for tools/attn_ab.py (results are WRONG when non-zero): 1 = no B fillers, 2 = no A
-// fillers, 4 = fragment reads only at the start of each phase, 8 = no LDS-DMA staging and no barrier in the tile loop.
 // MULC = false: the caller's Q already carries softmax_scale*log2(e) (the DiT's RMSNorm+RoPE kernel emits it that way, one
 // rounding) and scale_log2e is unused.  MULC = true (the public seam): Q is used as given and the factor is applied to the
 // fp32 scores inside B (one more VALU per score); all reference / threshold arithmetic is then in raw score units.
 // MODE: 0 = the complete kernel (reference maximum tracked per tile, deferred rescale).
 //       1 = OPTIMISTIC: the reference maximum of a row is fixed after tile 0 and never moves, so the per-score v_max3 stream (34 of the
-//           ~200 VALU instructions of a tile) and the per-tile decision disappear: -3.7 % on the C2 shape (tools/attn_abl.py, ABL 1024).
+//           ~200 VALU instructions of a tile) and the per-tile decision disappear: -3.7 % on the C2 shape (a timing ablation, code at e21fc0e).
 //           That is the same softmax as long as no exponential leaves fp32: the reference is the tile-0 maximum + SVI_OPT_HEADROOM (64), so with a
 //           row's scores up to 160 log2 units above its tile-0 maximum, P <= 2^96, the sums and O stay inside fp32 (bf16 P keeps 8 exponent bits),
 //           and numerator and denominator carry the same reference.  A row group whose sum reaches 2^96 (or is not a number: an exponential
@@ -899,7 +875,7 @@ __device__ __forceinline__ void pv_mfma(int& tok, u32x4 vf, u32x4 p, int& apin) 
 //       reference does not move there either); adversarial operands (tests: spikes, ramps, a late giant key) take the second pass.
 // QK8 (opt-in, SVI_ATTN_QK8): Q and K are MX e4m3 bytes (ldq / ldk in bytes) with their block-scale words qscale / kscale ([head][rows] dwords, byte b =
 //       channel block b of that head); QK^T runs on the scaled fp8 MFMA at twice the bf16 rate, everything behind the scores is unchanged.
-template <int TAG, int ABL = 0, bool MULC = false, int MODE = 0, bool QK8 = false>
+template <int TAG, bool MULC, int MODE, bool QK8>
 __global__ __launch_bounds__(256, 1) void flash_fwd2_kernel(const bf16* __restrict__ Q, int ldq,
                                                             const bf16* __restrict__ K, int ldk,
                                                             const bf16* __restrict__ VT, int ldvt,
@@ -907,24 +883,19 @@ __global__ __launch_bounds__(256, 1) void flash_fwd2_kernel(const bf16* __restri
                                                             float scale_log2e, int* __restrict__ flags,
                                                             float* __restrict__ opart, float2* __restrict__ ml, SviFlashSplit sp,
                                                             const unsigned* __restrict__ qscale, const unsigned* __restrict__ kscale, int qs_rows, int ks_rows) {
-#ifndef SVI_ABLATIONS
-    static_assert(!QK8 || ABL == 0, "ablations of the fp8 QK^T variant exist in variant builds only");
-#endif
     constexpr int EB = QK8 ? 1 : 2;             // bytes per Q / K element
     // QK8: the Q fragments are half the size (32 registers), so everything the kernel owns sits 32 registers higher and hipcc may park values in a[0:95]
     constexpr int OREG0 = QK8 ? SVI_OREG0 + 32 : SVI_OREG0, QREG0 = QK8 ? SVI_QREG0 + 32 : SVI_QREG0;
     constexpr bool OPT = MODE == 1;
-    // BAL (optimistic kernel only): one score per MFMA statement everywhere.  The optimistic pass never waits for a row maximum, so the
+    // OPT: one score per MFMA statement everywhere (the balanced schedule).  The optimistic pass never waits for a row maximum, so the
     // exponentials of tile t can start as soon as S(t) is complete: its 32 score pairs per lane are spread as
     //   4 pairs (key block 0, row group 0)             on statements 24..31 of phase 2 of tile t     (from sn; the only statements without B work before)
     //   16 pairs (kb 0 g 1, kb 1 g 0, kb 1 g 1, kb 2 g 0) on the 32 statements of phase 1 of tile t+1
     //   12 pairs (kb 2 g 1, kb 3 g 0, kb 3 g 1)         on statements 0..23 of phase 2 of tile t+1    (each before the PV statement that reads its word)
     // instead of 20 pairs on phase 1 (8 of its statements carrying a whole pair: 2 v_exp + 2 v_add + pack in one 32-cycle MFMA shadow,
     // more than fits) and 12 on phase 2.  Row sums run in four accumulators per lane over the whole key axis (no per-tile fold).
-    constexpr bool BAL = OPT && (ABL == 0 || QK8) && (SVI_FLASH_BALANCED != 0);      // (the fp8 variant's timing ablations keep the balanced schedule)
-    // rg(f, dma): the row-group statement (0 or 1) of fragment f behind which that fragment's look-ahead LDS read is issued: normally g = 0;
-    // where the g = 0 statement also issues an LDS-DMA piece (s_mov m0 + buffer_load ... lds on top of its score), the g = 1 statement
-    constexpr bool SPLIT = BAL && (SVI_FLASH_DMA_SPLIT != 0);
+    // A fragment's look-ahead LDS read sits behind its g = 0 statement, also where that statement issues an LDS-DMA piece: handing the read to
+    // the g = 1 statement instead measured 5.025 ms against 4.981 ms (profiles/r3e_attn_split_ab.txt; code at e21fc0e).
     // Work items are (q-block, head) pairs, q-block fastest.  Plain launch: a 2-D grid, one workgroup per item.  Split launch (sp.pieces > 1;
     // svi_launch_flash decides): a 1-D grid; the first sp.whole items run whole, every later item is cut along the key axis into
     // sp.pieces workgroups: piece z sees keys [k0, k1) — whole tiles — as if they were the whole problem and leaves its UNNORMALISED O
@@ -1116,13 +1087,13 @@ __global__ __launch_bounds__(256, 1) void flash_fwd2_kernel(const bf16* __restri
     // Statements k % 4 == 3 carry a whole pair (0..7), the other 24 one score each (pairs 8..19, EA then EB);
     // statements 4, 12, 20, 28 also issue the four LDS-DMA pieces of V(t) -> V stage VD.
     auto phase1 = [&](f32x16 (&sn)[2][2], f32x16 (&so)[2][2], auto ks_c, auto vs_c, auto vd_c, int t, auto with_b) {
-        constexpr bool WITH_B = decltype(with_b)::value && !(ABL & 1);
+        constexpr bool WITH_B = decltype(with_b)::value;
         constexpr int ks = decltype(ks_c)::value * KT_BYTES, vs = decltype(vs_c)::value * VT_BYTES;
         constexpr int vd = VST0 + decltype(vd_c)::value * VT_BYTES;
         const int so_v = t * KB * 2;
-        if constexpr (!BAL) ps[0][0] = ps[0][1] = ps[1][0] = ps[1][1] = 0.f;
+        if constexpr (!OPT) ps[0][0] = ps[0][1] = ps[1][0] = ps[1][1] = 0.f;
         if constexpr (QK8) {
-            // Eight statements k = 2 f' + g (f' = 2 tt + st) of 64 cycles.  BAL: each carries the two pairs 2k, 2k + 1 of the 16 this phase owes (same
+            // Eight statements k = 2 f' + g (f' = 2 tt + st) of 64 cycles.  OPT: each carries the two pairs 2k, 2k + 1 of the 16 this phase owes (same
             // order and words as the bf16 schedule); otherwise the statements are bare and the 20 pairs follow them as plain code (the complete kernel
             // only runs on flagged workgroups).  Statements 2, 3, 6, 7 issue the four pieces of V(t); fragment f' + 2 is read behind statement 2 f' + 1,
             // the first V^T fragments of phase 2 behind statements 5, 6, 7.
@@ -1134,12 +1105,12 @@ __global__ __launch_bounds__(256, 1) void flash_fwd2_kernel(const bf16* __restri
                 static_for<0, 2>([&](auto gc) {
                     constexpr int g = decltype(gc)::value;
                     constexpr int k = 2 * f + g;
-                    constexpr bool dma = st == 1 && !(ABL & 8);
+                    constexpr bool dma = st == 1;
                     constexpr int piece = tt * 2 + g;
                     int& pin = *((k == 1 || k == 3) ? &kaddr[2 * st] : &vaddr[0]);
                     const SviDma d = {v_rs, voff0, so_v + piece * vstep, piece0 + vd + 4096 * piece};
                     unsigned w0 = 0, w1 = 0;
-                    if constexpr (BAL && WITH_B) {
+                    if constexpr (OPT && WITH_B) {
                         constexpr int grp = k >> 1, wa = 2 * (k & 1);                  // pairs q1 = 2k, 2k + 1: group q1 >> 2, words q1 & 3
                         constexpr int pg = (grp == 0 || grp == 2) ? 1 : 0, tb = grp == 3 ? 1 : 0, psb = (grp == 1 || grp == 2) ? 1 : 0, r0 = 2 * (4 * psb + wa);
                         qk8_stmt<QREG0 + (g * 2 + st) * 8, st, st == 0, 2, dma, MULC>(tok, sn[g][tt], kfrag(f & 1), ksc[tt], qsc[g], pin, cneg[g], so[pg][tb][r0], so[pg][tb][r0 + 1],
@@ -1174,10 +1145,10 @@ __global__ __launch_bounds__(256, 1) void flash_fwd2_kernel(const bf16* __restri
                 constexpr int k = 2 * f + g;
                 // the register whose next use must stay behind this MFMA: the address of the fragment read that follows
                 int& pin = *((f + 3 < 16) ? &kaddr[f3 & 7] : &vaddr[0]);
-                constexpr bool dma = ((k & 7) == 4) && !(ABL & 8);
+                constexpr bool dma = (k & 7) == 4;
                 const SviDma d = {v_rs, voff0, so_v + ((k >> 3) & 3) * vstep, piece0 + vd + 4096 * ((k >> 3) & 3)};
                 unsigned wd = 0;
-                if constexpr (BAL) {
+                if constexpr (OPT) {
                     // pair k >> 1 of this phase: groups of four words — kb 0 g 1 | kb 1 g 0 | kb 1 g 1 | kb 2 g 0
                     constexpr int q1 = k >> 1, grp = q1 >> 2, w4 = q1 & 3;
                     constexpr int pg = (grp == 0 || grp == 2) ? 1 : 0, tb = grp == 3 ? 1 : 0, psb = (grp == 1 || grp == 2) ? 1 : 0, r0 = 2 * (4 * psb + w4);
@@ -1198,10 +1169,9 @@ __global__ __launch_bounds__(256, 1) void flash_fwd2_kernel(const bf16* __restri
                                                                                     dma ? d : no_dma);
                     if constexpr (fill == SVI_F_E2 || fill == SVI_F_EB) pw[pg][tb][w >> 2][w & 3] = wd;
                 }
-                constexpr int rg1 = (SPLIT && ((2 * f) & 7) == 4 && !(ABL & 8)) ? 1 : 0;       // this fragment's g = 0 statement carries a DMA piece
-                if constexpr (g == rg1 && f + 3 < 16 && !(ABL & 4))
+                if constexpr (g == 0 && f + 3 < 16)
                     kf[(f + 3) & 3] = *(lds_u32x4_t)(kaddr[f3 & 7] + ks + ((f + 3) >> 3) * 32 * 256);
-                if constexpr (g == rg1 && f + 3 >= 16)               // f = 13, 14, 15: V^T fragments 0, 1, 2 of phase 2
+                if constexpr (g == 0 && f + 3 >= 16)               // f = 13, 14, 15: V^T fragments 0, 1, 2 of phase 2
                     vf[f >= 13 ? f - 13 : 0] = *(lds_u32x4_t)(vaddr[0] + vs + (f >= 13 ? f - 13 : 0) * 32 * 128);
             });
         });
@@ -1214,14 +1184,14 @@ __global__ __launch_bounds__(256, 1) void flash_fwd2_kernel(const bf16* __restri
                       auto with_next) {
         constexpr bool MASKED = decltype(masked_tag)::value;
         constexpr bool WITH_PV = decltype(with_pv)::value;
-        constexpr bool WITH_B = WITH_PV && !(ABL & 1);
+        constexpr bool WITH_B = WITH_PV;
         constexpr bool WITH_NEXT = decltype(with_next)::value;
         constexpr int vs = decltype(vs_c)::value * VT_BYTES, kn = decltype(kn_c)::value * KT_BYTES;
         const int kd = ((t + 3) & 3) * KT_BYTES, so_k = (t + 3) * KB * ldk * EB;
         // MFMA result (the last QK^T MFMAs) -> VALU read, and VALU-written P -> MFMA operand: wait states by hand.  In the balanced optimistic
         // schedule nothing reads the new scores before statement 24 of this phase and the last P word written in phase 1 is first read by
-        // statement 16, so an unmasked tile needs no wait here (SVI_FLASH_SHORT_NOP=0 keeps the 16 states)
-        if constexpr (BAL && !MASKED && (SVI_FLASH_SHORT_NOP != 0)) asm("s_nop 0" : "+v"(tok), "+v"(sn[0][0]), "+v"(sn[0][1]), "+v"(sn[1][0]), "+v"(sn[1][1]));
+        // statement 16, so an unmasked tile needs no wait here
+        if constexpr (OPT && !MASKED) asm("s_nop 0" : "+v"(tok), "+v"(sn[0][0]), "+v"(sn[0][1]), "+v"(sn[1][0]), "+v"(sn[1][1]));
         else if constexpr (QK8) asm("s_nop 15\n\ts_nop 7" : "+v"(tok), "+v"(sn[0][0]), "+v"(sn[0][1]), "+v"(sn[1][0]), "+v"(sn[1][1]));      // a 16-pass MFMA's result
         else asm("s_nop 15" : "+v"(tok), "+v"(sn[0][0]), "+v"(sn[0][1]), "+v"(sn[1][0]), "+v"(sn[1][1]));
         if (MASKED) {
@@ -1246,10 +1216,10 @@ __global__ __launch_bounds__(256, 1) void flash_fwd2_kernel(const bf16* __restri
                 float& mch = (ia & 1) ? mb[ga] : ma[ga];
                 if constexpr (WITH_PV) {
                     int& pin = *((f + 3 < 16) ? &vaddr[f3 >> 2] : &kaddr[QK8 ? 2 * nf : nf]);
-                    constexpr bool dma = (j >= 24) && !(j & 1) && !(ABL & 8) && !(QK8 && j >= 28);       // QK8: a K tile is two pieces per wave
+                    constexpr bool dma = (j >= 24) && !(j & 1) && !(QK8 && j >= 28);       // QK8: a K tile is two pieces per wave
                     const SviDma d = {k_rs, koff0, so_k + ((j >> 1) & 3) * kstep, piece0 + kd + 4096 * ((j >> 1) & 3)};
                     unsigned wd = 0;
-                    if constexpr (BAL) {
+                    if constexpr (OPT) {
                         // statements 0..23: pairs of tile t-1 in the order the PV statements need their words — kb 2 g 1 | kb 3 g 0 | kb 3 g 1;
                         // statements 24..31: the first four pairs of THIS tile (kb 0, g 0; from sn) into the words PV statements 0..6 are done with
                         constexpr bool own = j >= 24;
@@ -1266,17 +1236,14 @@ __global__ __launch_bounds__(256, 1) void flash_fwd2_kernel(const bf16* __restri
                     constexpr int pi = 20 + (j >> 1);                // pairs 20..31 on statements 0..23
                     constexpr int pg = pi & 1, w = (pi >> 1) & 7, r0 = 2 * w;          // tb = 1
                     constexpr int fill = (!WITH_B || j >= 24) ? SVI_F_NONE : (j & 1) ? SVI_F_EB : SVI_F_EA;
-                    constexpr bool amax = !((ABL & 2) || (ABL & 32) || (ABL & 1024) || OPT);
-                    constexpr bool rest = amax || (ABL & 1024) || OPT;   // optimistic mode / ABL 1024: only the row-maximum pieces are left out
-                    pv_stmt<OREG0 + (g * 4 + d4) * 16, amax, rest ? fill : SVI_F_NONE, rest && dma, MULC>(
+                    pv_stmt<OREG0 + (g * 4 + d4) * 16, true, fill, dma, MULC>(
                         tok, vf[f & 3], vf[((f & 1) || f == 15) ? (f & 3) : ((f + 1) & 3)], pw[g][tt][sb], pin, mch, sn[ga][ta][ra], sn[ga][ta][ra + 1], so[pg][1][r0], so[pg][1][r0 + 1],
                         scale_log2e, tcar, ps[pg][0], ps[pg][1], wd, dma ? d : no_dma);
-                    if constexpr (rest && fill == SVI_F_EB) pw[pg][1][w >> 2][w & 3] = wd;
+                    if constexpr (fill == SVI_F_EB) pw[pg][1][w >> 2][w & 3] = wd;
                     }
-                    constexpr int rg2 = (SPLIT && f >= 12 && !(ABL & 8)) ? 1 : 0;               // statements 24, 26, 28, 30 carry the K pieces
-                    if constexpr (g == rg2 && f + 3 < 16 && !(ABL & 4))
+                    if constexpr (g == 0 && f + 3 < 16)
                         vf[(f + 3) & 3] = *(lds_u32x4_t)(vaddr[f3 >> 2] + vs + (f3 & 3) * 32 * 128);
-                    if constexpr (g == rg2 && f + 3 >= 16 && WITH_NEXT) {
+                    if constexpr (g == 0 && f + 3 >= 16 && WITH_NEXT) {
                         if constexpr (!QK8) kf[nf] = *(lds_u32x4_t)(kaddr[nf] + kn);
                         else if constexpr (nf < 2) {         // fragments 0 and 1 of tile t+1 (key block 0, both 64-channel steps)
                             kf[2 * nf] = *(lds_u32x4_t)(kaddr[2 * nf] + kn);
@@ -1286,10 +1253,10 @@ __global__ __launch_bounds__(256, 1) void flash_fwd2_kernel(const bf16* __restri
                             ksw[1] = *(lds_u32_t)(kaddr[4] + kn + 128);
                         }
                     }
-                    if constexpr (QK8 && j == 28 && !(ABL & 8))   // the scale words of K(t+3): one dword per lane, behind the tile's two K pieces
+                    if constexpr (QK8 && j == 28)   // the scale words of K(t+3): one dword per lane, behind the tile's two K pieces
                         asm volatile("s_mov_b32 m0, %[m0v]\n\ts_nop 0\n\tbuffer_load_dword %[vo], %[rs], %[so] offen lds"
                                      : "+v"(tok) : [m0v] "s"(lds0 + kd + KSC_OFF), [vo] "v"(lane * 4), [rs] "s"(ks_rs), [so] "s"((t + 3) * KB * 4));
-                    if constexpr (WITH_B && j == 23 && !BAL) {       // all 32 pairs of tile t-1 are done: fold the row sums
+                    if constexpr (WITH_B && j == 23 && !OPT) {       // all 32 pairs of tile t-1 are done: fold the row sums
                         l_run[0] = l_run[0] * alpha[0] + (ps[0][0] + ps[0][1]);
                         l_run[1] = l_run[1] * alpha[1] + (ps[1][0] + ps[1][1]);
                         alpha[0] = alpha[1] = 1.0f;
@@ -1312,9 +1279,9 @@ __global__ __launch_bounds__(256, 1) void flash_fwd2_kernel(const bf16* __restri
     };
     // does some row of this wave exceed its reference by more than the threshold?  (per-lane maxima are enough to decide)
     auto outgrown = [&]() -> bool {
-        if constexpr ((ABL & 2) || (ABL & 16) || (ABL & 1024) || OPT) return false;
+        if constexpr (OPT) return false;
         const float mx = vmax3(ma[0], mb[0], vmax3(ma[1], mb[1], mb[1]));
-        return __any(mx * cs > ((ABL & 128) ? 1e30f : SVI_RESCALE_THR));
+        return __any(mx * cs > SVI_RESCALE_THR);
     };
     // Move the reference maximum of both row groups by delta[g] (first tile: any sign, later >= 0): the -M tuples, the scores
     // of the tile whose exponentials are still pending (sn, computed against the old reference) and alpha for O and l.
@@ -1362,16 +1329,14 @@ __global__ __launch_bounds__(256, 1) void flash_fwd2_kernel(const bf16* __restri
         for (int kk = 0; kk < 8; ++kk) kaddr[kk] ^= 2 * KT_BYTES;      // this tile's K reads are done: move to the other half
         phase2(sB, sA, I0{}, I0{}, t, masked_tag, std::true_type{}, with_next);
         const bool need = outgrown();
-        if constexpr (!(ABL & 256)) tile_barrier<QK8 ? 3 : 4>(tok);
-        if constexpr ((ABL & 256) && !(ABL & 512)) asm volatile("s_waitcnt vmcnt(4)" : "+v"(tok) :: "memory");
+        tile_barrier<QK8 ? 3 : 4>(tok);
         return need;
     };
     auto tile_even = [&](int t, auto masked_tag, auto with_next) -> bool {
         phase1(sA, sB, I0{}, I1{}, I0{}, t, std::true_type{});
         phase2(sA, sB, I1{}, I1{}, t, masked_tag, std::true_type{}, with_next);
         const bool need = outgrown();
-        if constexpr (!(ABL & 256)) tile_barrier<QK8 ? 3 : 4>(tok);
-        if constexpr ((ABL & 256) && !(ABL & 512)) asm volatile("s_waitcnt vmcnt(4)" : "+v"(tok) :: "memory");
+        tile_barrier<QK8 ? 3 : 4>(tok);
         return need;
     };
 
@@ -1423,7 +1388,7 @@ __global__ __launch_bounds__(256, 1) void flash_fwd2_kernel(const bf16* __restri
         const float d0[2] = {row_max(0) + hr, row_max(1) + hr};
         commit(sA, d0);
         alpha[0] = alpha[1] = 1.0f;                                    // O and l are still 0
-        if constexpr (BAL) {      // the four pairs a later tile handles on statements 24..31 of its own phase 2 (kb 0, g 0), for tile 0
+        if constexpr (OPT) {      // the four pairs a later tile handles on statements 24..31 of its own phase 2 (kb 0, g 0), for tile 0
 #pragma unroll
             for (int w4 = 0; w4 < 4; ++w4) {
                 const float p0 = __builtin_amdgcn_exp2f(sA[0][0][2 * w4] * cs);
@@ -1469,13 +1434,13 @@ __global__ __launch_bounds__(256, 1) void flash_fwd2_kernel(const bf16* __restri
             for (int tt = 0; tt < 2; ++tt)
 #pragma unroll
                 for (int r = 0; r < 16; r += 2) {
-                    if (BAL && g == 0 && tt == 0 && r < 8) continue;      // already done (and summed) on statements 24..31 of the last phase 2
+                    if (OPT && g == 0 && tt == 0 && r < 8) continue;      // already done (and summed) on statements 24..31 of the last phase 2
                     const float p0 = __builtin_amdgcn_exp2f(sB[g][tt][r] * cs);
                     const float p1 = __builtin_amdgcn_exp2f(sB[g][tt][r + 1] * cs);
                     psd[g] += p0 + p1;
                     pw[g][tt][r >> 3][(r & 7) >> 1] = pack_bf16x2(p0, p1);
                 }
-            if constexpr (BAL) l_run[g] = (ps[g][0] + ps[g][1]) + psd[g];      // four running sums per lane over the whole key axis
+            if constexpr (OPT) l_run[g] = (ps[g][0] + ps[g][1]) + psd[g];      // four running sums per lane over the whole key axis
             else l_run[g] = l_run[g] * alpha[g] + psd[g];
         }
         asm("s_nop 1" : "+v"(tok), "+v"(pw[0][0][0]), "+v"(pw[0][0][1]), "+v"(pw[0][1][0]), "+v"(pw[0][1][1]));
@@ -1650,9 +1615,6 @@ __device__ __forceinline__ void s3_settle(int& tok, f32x4 (&s)[4][4]) {
     asm volatile("s_nop 15" : "+v"(tok), "+v"(s[0][0]), "+v"(s[0][1]), "+v"(s[0][2]), "+v"(s[0][3]), "+v"(s[1][0]), "+v"(s[1][1]), "+v"(s[1][2]), "+v"(s[1][3]),
                               "+v"(s[2][0]), "+v"(s[2][1]), "+v"(s[2][2]), "+v"(s[2][3]), "+v"(s[3][0]), "+v"(s[3][1]), "+v"(s[3][2]), "+v"(s[3][3]));
 }
-#ifndef SVI3_ABL
-#define SVI3_ABL 0          // timing ablations of variant builds (tools/build_variant.py attn_ablN -DSVI3_ABL=N; results WRONG): 1 no LDS-DMA in the tile loop, 2 no softmax fillers (and no LDS-DMA), 4 no tile barrier, 8 no look-ahead fragment reads
-#endif
 template <int TAG, bool MULC>
 __global__ __launch_bounds__(256, 1) void flash_fwd3_kernel(const bf16* __restrict__ Q, int ldq, const bf16* __restrict__ K, int ldk, const bf16* __restrict__ VT, int ldvt,
                                                             bf16* __restrict__ O, int ldo, int Lq, int Lk, float scale_log2e, int* __restrict__ flags,
@@ -1782,14 +1744,13 @@ __global__ __launch_bounds__(256, 1) void flash_fwd3_kernel(const bf16* __restri
             constexpr int kb = f >> 2, ds = f & 3, f3 = f + 5;
             constexpr int kbp = f < 8 ? 1 : 2, qbp = (f & 7) >> 1, ep = f & 1;            // this fragment's score pair
             int& pin = *((f3 < 16) ? &kaddr[f3 & 3] : &vaddr[0]);
-            constexpr bool dma = ds == 2 && !(SVI3_ABL & 3);
+            constexpr bool dma = ds == 2;
             const SviDma d = {v_rs, vvo[kb], so_v, piece0 + vd};
             unsigned wd = 0;
-            qk3_frag<QREG0 + ds * 4, ds == 0, !(SVI3_ABL & 2), dma, MULC, 4096 * kb>(tok, sn[kb][0], sn[kb][1], sn[kb][2], sn[kb][3], kf[f % 6], kf[((f & 1) || f == 15) ? (f % 6) : ((f + 1) % 6)], pin,
+            qk3_frag<QREG0 + ds * 4, ds == 0, true, dma, MULC, 4096 * kb>(tok, sn[kb][0], sn[kb][1], sn[kb][2], sn[kb][3], kf[f % 6], kf[((f & 1) || f == 15) ? (f % 6) : ((f + 1) % 6)], pin,
                                                                 cneg[0], cneg[1], cneg[2], cneg[3], so[kbp][qbp][2 * ep], so[kbp][qbp][2 * ep + 1], scale_log2e, ps[qbp][0], ps[qbp][1],
                                                                 wd, dma ? d : no_dma);
             pw[kbp >> 1][qbp][2 * (kbp & 1) + ep] = wd;
-            if constexpr (SVI3_ABL & 8) return;
             if constexpr (f3 < 16) kf[f3 % 6] = *(lds_u32x4_t)(kaddr[f3 & 3] + ks + SVI3_KBO(f3 >> 2));
             else vf[f3 - 16] = *(lds_u32x4_t)(vaddr[0] + vs + (f3 - 16) * 16 * 128);
         });
@@ -1819,15 +1780,14 @@ __global__ __launch_bounds__(256, 1) void flash_fwd3_kernel(const bf16* __restri
             constexpr int qbp = (f & 7) >> 1, ep = f & 1;
             constexpr int nf = f3 < 16 ? 0 : f3 - 16;              // the next tile's K fragment read behind this one (key block nf >> 2, channel step nf & 3)
             int& pin = *((f3 < 16) ? &vaddr[f3 >> 3] : &kaddr[nf & 3]);
-            constexpr bool dma = f >= 12 && !(SVI3_ABL & 3);
+            constexpr bool dma = f >= 12;
             constexpr int pj = f >= 12 ? f - 12 : 0;              // K piece issued inside this fragment's block
             const SviDma d = {k_rs, kvo[pj], so_k, piece0 + kd};
             unsigned wd = 0;
-            pv3_frag<OREG0 + db * 16, !(SVI3_ABL & 2), dma, MULC, 4096 * pj>(tok, vf[f % 6], vf[((f & 1) || f == 15) ? (f % 6) : ((f + 1) % 6)], pw[ks2][0], pw[ks2][1], pw[ks2][2], pw[ks2][3], pin,
+            pv3_frag<OREG0 + db * 16, true, dma, MULC, 4096 * pj>(tok, vf[f % 6], vf[((f & 1) || f == 15) ? (f % 6) : ((f + 1) % 6)], pw[ks2][0], pw[ks2][1], pw[ks2][2], pw[ks2][3], pin,
                                                         own ? sn[0][qbp][2 * ep] : so[3][qbp][2 * ep], own ? sn[0][qbp][2 * ep + 1] : so[3][qbp][2 * ep + 1], scale_log2e,
                                                         ps[qbp][0], ps[qbp][1], wd, dma ? d : no_dma);
             pw[own ? 0 : 1][qbp][(own ? 0 : 2) + ep] = wd;
-            if constexpr (SVI3_ABL & 8) return;
             if constexpr (f3 < 16) vf[f3 % 6] = *(lds_u32x4_t)(vaddr[f3 >> 3] + vs + (f3 & 7) * 16 * 128);
             else if constexpr (WITH_NEXT) kf[nf] = *(lds_u32x4_t)(kaddr[nf & 3] + kn + SVI3_KBO(nf >> 2));
         });
@@ -1839,12 +1799,12 @@ __global__ __launch_bounds__(256, 1) void flash_fwd3_kernel(const bf16* __restri
 #pragma unroll
         for (int ds = 0; ds < 4; ++ds) kaddr[ds] ^= 2 * KT_BYTES;
         phase2(sB, sA, I0{}, I0{}, t, masked_tag, with_next);
-        if constexpr (!(SVI3_ABL & 4)) tile_barrier<(SVI3_ABL & 3) ? 0 : 4>(tok);
+        tile_barrier<4>(tok);
     };
     auto tile_even = [&](int t, auto masked_tag, auto with_next) __attribute__((always_inline)) {
         phase1(sA, sB, I0{}, I1{}, I0{}, t);
         phase2(sA, sB, I1{}, I1{}, t, masked_tag, with_next);
-        if constexpr (!(SVI3_ABL & 4)) tile_barrier<(SVI3_ABL & 3) ? 0 : 4>(tok);
+        tile_barrier<4>(tok);
     };
 
     // ---- prologue: K(0..3) and V(0) staged; tile 0: scores, the rows' reference, its first key block's pairs ----
@@ -2237,61 +2197,20 @@ svi_status svi_launch_flash(const bf16* Q, int ldq, const bf16* K, int ldk, cons
         const long nwg = (long)grid2.x * grid2.y;
         // optimistic pass + flagged second pass (see the kernel's MODE): needs the per-device flag words
         int* flags = nullptr;
-        bool two_pass = sw.flash_two_pass != 0 && nwg <= SVI_FLASH_MAX_FLAGS;
-#ifdef SVI_ABLATIONS
-        if (sw.flash_abl && !qk8) two_pass = false;
-#endif
+        const bool two_pass = sw.flash_two_pass != 0 && nwg <= SVI_FLASH_MAX_FLAGS;
         if (two_pass) SVI_TRY(flash_flags(st, nwg, &flags));
         kern_t kern;
         if (qk8)
-            kern = two_pass ? (q_prescaled ? flash_fwd2_kernel<0, 0, false, 1, true> : flash_fwd2_kernel<0, 0, true, 1, true>)
-                            : (q_prescaled ? flash_fwd2_kernel<0, 0, false, 0, true> : flash_fwd2_kernel<0, 0, true, 0, true>);
+            kern = two_pass ? (q_prescaled ? flash_fwd2_kernel<0, false, 1, true> : flash_fwd2_kernel<0, true, 1, true>)
+                            : (q_prescaled ? flash_fwd2_kernel<0, false, 0, true> : flash_fwd2_kernel<0, true, 0, true>);
         else if (two_pass)
-            kern = q_prescaled ? (Lq == Lk ? flash_fwd2_kernel<0, 0, false, 1> : flash_fwd2_kernel<1, 0, false, 1>)
-                               : (Lq == Lk ? flash_fwd2_kernel<0, 0, true, 1> : flash_fwd2_kernel<1, 0, true, 1>);
+            kern = q_prescaled ? (Lq == Lk ? flash_fwd2_kernel<0, false, 1, false> : flash_fwd2_kernel<1, false, 1, false>)
+                               : (Lq == Lk ? flash_fwd2_kernel<0, true, 1, false> : flash_fwd2_kernel<1, true, 1, false>);
         else
-            kern = q_prescaled ? (Lq == Lk ? flash_fwd2_kernel<0, 0, false> : flash_fwd2_kernel<1, 0, false>)
-                               : (Lq == Lk ? flash_fwd2_kernel<0, 0, true> : flash_fwd2_kernel<1, 0, true>);
-#ifdef SVI_ABLATIONS       // timing-only ablations (tools/attn_abl.py; results wrong), see the kernel's ABL parameter: variant builds only
-        switch ((q_prescaled && !qk8) ? sw.flash_abl : 0) {
-            case 1: kern = flash_fwd2_kernel<0, 1>; break;
-            case 2: kern = flash_fwd2_kernel<0, 2>; break;
-            case 3: kern = flash_fwd2_kernel<0, 3>; break;
-            case 4: kern = flash_fwd2_kernel<0, 4>; break;
-            case 7: kern = flash_fwd2_kernel<0, 7>; break;
-            case 8: kern = flash_fwd2_kernel<0, 8>; break;
-            case 15: kern = flash_fwd2_kernel<0, 15>; break;
-            case 16: kern = flash_fwd2_kernel<0, 16>; break;
-            case 32: kern = flash_fwd2_kernel<0, 32>; break;
-            case 64: kern = flash_fwd2_kernel<0, 64>; break;
-            case 128: kern = flash_fwd2_kernel<0, 128>; break;
-            case 256: kern = flash_fwd2_kernel<0, 256>; break;
-            case 768: kern = flash_fwd2_kernel<0, 768>; break;
-            case 1024: kern = flash_fwd2_kernel<0, 1024>; break;
-            case 1025: kern = flash_fwd2_kernel<0, 1025>; break;      // the combinations below: on top of the optimistic loop (1024)
-            case 1028: kern = flash_fwd2_kernel<0, 1028>; break;
-            case 1032: kern = flash_fwd2_kernel<0, 1032>; break;
-            case 1280: kern = flash_fwd2_kernel<0, 1280>; break;
-            case 1792: kern = flash_fwd2_kernel<0, 1792>; break;
-            case 1039: kern = flash_fwd2_kernel<0, 1039>; break;
-            default: break;
-        }
-#endif
-#ifdef SVI_ABLATIONS       // timing-only ablations of the optimistic fp8 kernel (tools/attn_qk8_abl.py; results wrong): 1 no softmax fillers, 8 no LDS-DMA, 256 no barrier
-        if (qk8 && two_pass && q_prescaled) switch (sw.flash_abl) {
-            case 1: kern = flash_fwd2_kernel<0, 1, false, 1, true>; break;
-            case 8: kern = flash_fwd2_kernel<0, 8, false, 1, true>; break;
-            case 9: kern = flash_fwd2_kernel<0, 9, false, 1, true>; break;
-            case 264: kern = flash_fwd2_kernel<0, 264, false, 1, true>; break;
-            case 265: kern = flash_fwd2_kernel<0, 265, false, 1, true>; break;
-            default: break;
-        }
-#endif
+            kern = q_prescaled ? (Lq == Lk ? flash_fwd2_kernel<0, false, 0, false> : flash_fwd2_kernel<1, false, 0, false>)
+                               : (Lq == Lk ? flash_fwd2_kernel<0, true, 0, false> : flash_fwd2_kernel<1, true, 0, false>);
         // the optimistic pass on v_mfma_f32_16x16x32_bf16 (flash_fwd3_kernel; SVI_FLASH_M16 = 0: flash_fwd2_kernel<.., 1>, the 32x32x16 form): same grid, flags and outputs
-        bool m16 = two_pass && !qk8 && sw.flash_m16 != 0;
-#ifdef SVI_ABLATIONS
-        if (sw.flash_abl) m16 = false;
-#endif
+        const bool m16 = two_pass && !qk8 && sw.flash_m16 != 0;
         if (m16) {
             typedef void (*kern3_t)(const bf16*, int, const bf16*, int, const bf16*, int, bf16*, int, int, int, float, int*, float*, float2*, SviFlashSplit);
             const kern3_t k3 = q_prescaled ? (Lq == Lk ? flash_fwd3_kernel<0, false> : flash_fwd3_kernel<1, false>) : (Lq == Lk ? flash_fwd3_kernel<0, true> : flash_fwd3_kernel<1, true>);
@@ -2303,9 +2222,9 @@ svi_status svi_launch_flash(const bf16* Q, int ldq, const bf16* K, int ldk, cons
         }
         SVI_LAUNCH_CHECK();
         if (two_pass) {
-            kern_t safe = q_prescaled ? (Lq == Lk ? flash_fwd2_kernel<0, 0, false, 2> : flash_fwd2_kernel<1, 0, false, 2>)
-                                      : (Lq == Lk ? flash_fwd2_kernel<0, 0, true, 2> : flash_fwd2_kernel<1, 0, true, 2>);
-            if (qk8) safe = q_prescaled ? flash_fwd2_kernel<0, 0, false, 2, true> : flash_fwd2_kernel<0, 0, true, 2, true>;
+            kern_t safe = q_prescaled ? (Lq == Lk ? flash_fwd2_kernel<0, false, 2, false> : flash_fwd2_kernel<1, false, 2, false>)
+                                      : (Lq == Lk ? flash_fwd2_kernel<0, true, 2, false> : flash_fwd2_kernel<1, true, 2, false>);
+            if (qk8) safe = q_prescaled ? flash_fwd2_kernel<0, false, 2, true> : flash_fwd2_kernel<0, true, 2, true>;
             SVI_TRY(svi_ensure_lds(reinterpret_cast<const void*>(safe), lds2));
             hipLaunchKernelGGL(safe, grid2, block2, lds2, st, Q, ldq, K, ldk, VT, ldvt, O, ldo, Lq, Lk, scale_log2e, flags, opart, ml, sp, qsc, ksc, qs_rows, ks_rows);
             SVI_LAUNCH_CHECK();

@@ -56,8 +56,7 @@ void svi_set_error(const char* fmt, ...);
 
 // ---- process-wide switches, read ONCE (first use) ------------------------------------------------
 // A/B aids that select between kernels computing the SAME result (bit-identical or within the stated parity bounds); they
-// never change what is computed.  Switches that make results wrong (timing ablations) exist only in variant builds made with
-// -DSVI_ABLATIONS (tools/build_variant.py) and are absent from the product library.
+// never change what is computed.
 struct SviSwitches {
     int flash_kernel = 0;        // SVI_FLASH_KERNEL = 1 | 2 : force flash_fwd_kernel / flash_fwd2_kernel (0: by key count)
     int gemm_kernel = 0;         // SVI_GEMM_KERNEL = 128 | 192 | 259 | 260 : force the 128^2 kernel / the 256 x 192 tile / the 256^2 tile with four / two phases per K tile (0: by tile count)
@@ -99,9 +98,6 @@ struct SviSwitches {
                                  // reference module computes on a CPU — the arithmetic the committed fixtures were made with) instead of the device's
     int ws_limit_mb = 0;         // SVI_WS_LIMIT_MB = n : a DiT workspace beyond n MiB is refused as if the allocation had failed (SVI_ERR_OOM): a budget for callers who
                                  // share the device, and the way tests reach the stacked CFG pair's out-of-memory fall-back without exhausting a 288 GB part
-#ifdef SVI_ABLATIONS
-    int flash_abl = 0, gemm_epi_abl = 0, vae_abl = 0, flash_assume_prescaled = 0;
-#endif
 };
 const SviSwitches& svi_switches();
 

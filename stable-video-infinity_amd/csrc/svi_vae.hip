@@ -47,7 +47,7 @@ struct ConvP {
     int zero_frame0;                                 // input frame 0 reads as zeros
     int t_begin;                                     // first output frame computed
     int out_mode;                                    // 0: out[t,y,x,co]   1: time interleave (see epilogue)
-    int abl;                                         // timing ablations of conv_igemm_x3_kernel (SVI_VAE_ABL; results wrong): 1 no global loads, 2 no LDS stores, 4 no MFMAs, 8 no epilogue, 16 no K loop
+    int pad_;                                        // unused: keeps the argument offsets of the fields below, and so the kernels' code, as they were
     int t_out_off;                                   // added to the output frame index (mode 0)
     const float* res; int ld_res;                    // optional residual, same pixel indexing as out (mode 0)
     int act_silu;                                    // conv_igemm_kernel, mode 0: out = silu(conv + bias)  (pose embedder)
@@ -265,13 +265,6 @@ __device__ __forceinline__ void split2h_pair(float x0, float x1, float s, unsign
         : [h] "=&v"(h), [l] "=v"(l), [r0] "=&v"(r0), [r1] "=&v"(r1) : [x0] "v"(x0), [x1] "v"(x1), [s] "s"(s));
 }
 
-// timing ablations (tools/vae_ab.py, SVI_VAE_ABL): compiled in only with -DSVI_ABLATIONS so that the product kernel has no
-// branches inside a K step
-#ifdef SVI_ABLATIONS
-#define SVI_X3_ABL(bit) (p.abl & (bit))
-#else
-#define SVI_X3_ABL(bit) false
-#endif
 template <bool H2>
 __global__ __launch_bounds__(512, 2) void conv_igemm_x3_kernel(ConvP p) {
     constexpr int NPL = H2 ? 2 : 3;                                   // operand planes
@@ -446,21 +439,19 @@ __global__ __launch_bounds__(512, 2) void conv_igemm_x3_kernel(ConvP p) {
     } while (0)
 #define SVI_X3_STORES(SS, SBUF)                                                                                                          \
     do {                                                                                                                         \
-        if (!SVI_X3_ABL(2)) {                                                                                                    \
-            if (s_ < 4) {                                                                                                        \
-                char* As_ = smem + (SBUF) * STAGE;                                                                               \
-                const int off_ = x3_off((tid >> 3) + 64 * s_, a_c4 >> 1) + (a_c4 & 1) * 8;                                       \
-                if constexpr (H2) {                                                                                              \
-                    *reinterpret_cast<u32x2*>(As_ + off_) = u32x2{hp_[0], hp_[1]};                                               \
-                    *reinterpret_cast<u32x2*>(As_ + X3_A_PLANE + off_) = u32x2{lp_[0], lp_[1]};                                  \
-                } else {                                                                                                         \
-                    *reinterpret_cast<u16x4*>(As_ + off_) = hq_;                                                                 \
-                    *reinterpret_cast<u16x4*>(As_ + X3_A_PLANE + off_) = mq_;                                                    \
-                    *reinterpret_cast<u16x4*>(As_ + 2 * X3_A_PLANE + off_) = lq_;                                                \
-                }                                                                                                                \
-            } else if (s_ == 4) { SVI_X3_STAGE_W(SS, SBUF, 0); SVI_X3_STAGE_W(SS, SBUF, 1); }                                    \
-            else SVI_X3_STAGE_W(SS, SBUF, 2);                                                                                    \
-        }                                                                                                                        \
+        if (s_ < 4) {                                                                                                            \
+            char* As_ = smem + (SBUF) * STAGE;                                                                                   \
+            const int off_ = x3_off((tid >> 3) + 64 * s_, a_c4 >> 1) + (a_c4 & 1) * 8;                                           \
+            if constexpr (H2) {                                                                                                  \
+                *reinterpret_cast<u32x2*>(As_ + off_) = u32x2{hp_[0], hp_[1]};                                                   \
+                *reinterpret_cast<u32x2*>(As_ + X3_A_PLANE + off_) = u32x2{lp_[0], lp_[1]};                                      \
+            } else {                                                                                                             \
+                *reinterpret_cast<u16x4*>(As_ + off_) = hq_;                                                                     \
+                *reinterpret_cast<u16x4*>(As_ + X3_A_PLANE + off_) = mq_;                                                        \
+                *reinterpret_cast<u16x4*>(As_ + 2 * X3_A_PLANE + off_) = lq_;                                                    \
+            }                                                                                                                    \
+        } else if (s_ == 4) { SVI_X3_STAGE_W(SS, SBUF, 0); SVI_X3_STAGE_W(SS, SBUF, 1); }                                        \
+        else SVI_X3_STAGE_W(SS, SBUF, 2);                                                                                        \
     } while (0)
 #define SVI_X3_LOADS(SI)                                                                                                           \
     do {                                                                                                                         \
@@ -475,7 +466,7 @@ __global__ __launch_bounds__(512, 2) void conv_igemm_x3_kernel(ConvP p) {
     do {                                                                                                                         \
         const int cc_ = it_cc;                                                                                                   \
         const int c_ = cc_ * 32 + a_c4 * 4;                                                                                      \
-        const bool wvalid_ = (valid) && !SVI_X3_ABL(1);                                                                          \
+        const bool wvalid_ = (valid);                                                                                           \
         const bool cin_ = wvalid_ && c_ < p.Cin;                                                                                 \
         const unsigned wk_ = it_wk;                                                                                              \
         const char* As_c = smem + (CBUF) * STAGE;                                                                                \
@@ -551,7 +542,7 @@ __global__ __launch_bounds__(512, 2) void conv_igemm_x3_kernel(ConvP p) {
     {
         const int cc_ = 0;
         const int c_ = a_c4 * 4;
-        const bool wvalid_ = !SVI_X3_ABL(1), cin_ = wvalid_ && c_ < p.Cin;
+        const bool wvalid_ = true, cin_ = c_ < p.Cin;
         const unsigned wk_ = 0;
 #pragma unroll
         for (int j = 0; j < 4; ++j) SVI_X3_LOAD_A(0, j);
@@ -564,7 +555,7 @@ __global__ __launch_bounds__(512, 2) void conv_igemm_x3_kernel(ConvP p) {
     {
         const int cc_ = it_cc;
         const int c_ = cc_ * 32 + a_c4 * 4;
-        const bool wvalid_ = nk > 1 && !SVI_X3_ABL(1), cin_ = wvalid_ && c_ < p.Cin;
+        const bool wvalid_ = nk > 1, cin_ = wvalid_ && c_ < p.Cin;
         const unsigned wk_ = it_wk;
 #pragma unroll
         for (int j = 0; j < 4; ++j) SVI_X3_LOAD_A(1, j);
@@ -572,8 +563,7 @@ __global__ __launch_bounds__(512, 2) void conv_igemm_x3_kernel(ConvP p) {
     }
     SVI_X3_ADVANCE();
     __syncthreads();
-    const int nkk = SVI_X3_ABL(16) ? 0 : nk;
-    for (int k = 0; k < nkk; k += 2) {
+    for (int k = 0; k < nk; k += 2) {
         SVI_X3_STEP(0, 0, k + 2, k + 2 < nk, 1, 1);      // compute stage 0 | stage set 1 (step k+1) -> stage 1 | load step k+2 -> set 0
         __syncthreads();
         SVI_X3_STEP(1, 1, k + 3, k + 3 < nk, 0, 0);      // compute stage 1 | stage set 0 (step k+2) -> stage 0 | load step k+3 -> set 1
@@ -596,7 +586,6 @@ __global__ __launch_bounds__(512, 2) void conv_igemm_x3_kernel(ConvP p) {
     // dependent ones — the same fix as the GEMM epilogue's), then added and stored.
     const long pp = p0 + 32 * wave + l31;
     if (pp >= P_total) return;
-    if (SVI_X3_ABL(8) && acc[0][0] != 123.456f) return;
     const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
     f32x4 bv[12], rv[12], sv[12];
     const bool with_res = p.out_mode == 0 && p.res;
@@ -1218,9 +1207,6 @@ svi_status launch_conv(const ConvP& p, hipStream_t st) {
     if (conv_x3_ok(p)) {
         dim3 grid3((unsigned)((pixels + X3_PIX - 1) / X3_PIX), (unsigned)((p.Cout + X3_CO - 1) / X3_CO)), block3(512);
         ConvP pa = p;
-#ifdef SVI_ABLATIONS
-        pa.abl = svi_switches().vae_abl;
-#endif
         if (p.w2h && p.w2_inv && p.in_scale > 0.f && !svi_switches().vae_no_x2h && (((uintptr_t)p.w2_inv) & 15) == 0 && p.Cin % 32 == 0 && !p.ups && !p.up_phase &&
             (long)(p.kt + 3) * p.Hi * p.Wi * p.ld_in * 4 < 0xFFE00000L && (long)2 * p.plane_w3 * 2 < 0xFFE00000L) {
             SVI_TRY(svi_ensure_lds(reinterpret_cast<const void*>(conv_igemm_x3_kernel<true>), 2 * X2H_STAGE));

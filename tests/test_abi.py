@@ -77,14 +77,19 @@ def test_ops_fail_loudly_without_gpu():
 
 def test_every_environment_switch_is_documented():
     """Each SVI_* switch the library parses (csrc/svi_api.hip) is listed in the public header and explained where its field lives
-    (csrc/svi_common.h SviSwitches); the timing ablations of variant builds (-DSVI_ABLATIONS) are the exception: they are not in the product."""
+    (csrc/svi_common.h SviSwitches).  Timing ablations are not in the product source: none of their switches or macros occurs under csrc/."""
     import os
     import re
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    src = open(os.path.join(root, "stable-video-infinity_amd", "csrc", "svi_api.hip")).read()
-    product, _, ablations = src.partition("#ifdef SVI_ABLATIONS\n    s.flash_abl")
-    names = set(re.findall(r'(?:env_int|getenv)\("(SVI_[A-Z0-9_]+)"', product))
+    csrc = os.path.join(root, "stable-video-infinity_amd", "csrc")
+    src = open(os.path.join(csrc, "svi_api.hip")).read()
+    parse = re.search(r"\nstatic SviSwitches parse_switches\(\) \{\n.*?\n\}\n", src, re.S).group(0)
+    names = set(re.findall(r'(?:env_int|getenv)\("(SVI_[A-Z0-9_]+)"', parse))
     assert len(names) >= 14 and "SVI_FLASH_ABL" not in names
+    removed = re.compile(r"SVI_ABLATIONS|SVI3_ABL|SVI_GEMM_EXPERIMENTS|SVI_W4_|SVI_FLASH_(DMA_SPLIT|SUM_DOT2|BALANCED|SHORT_NOP|ABL|ASSUME_PRESCALED)|SVI_(GEMM_EPI|VAE)_ABL")
+    for f in sorted(os.listdir(csrc)):
+        if f.endswith((".hip", ".h")):
+            assert not removed.search(open(os.path.join(csrc, f)).read()), f
     header = open(os.path.join(root, "include", "svi_hip.h")).read()
     common = open(os.path.join(root, "stable-video-infinity_amd", "csrc", "svi_common.h")).read()
     missing = sorted(n for n in names if n not in header or n not in common)

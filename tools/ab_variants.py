@@ -1,5 +1,5 @@
 """Run one tool alternately under two builds of the library on the SAME box (box-to-box variance on this pool is up to 20 %).
-    python tools/ab_variants.py NAME rounds -- python tools/attn_abl.py 3"""
+    python tools/ab_variants.py NAME rounds -- python tools/attn_stats.py --quick --a-only"""
 import os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 name, rounds = sys.argv[1], int(sys.argv[2]); cmd = sys.argv[sys.argv.index("--") + 1:]

@@ -3,7 +3,7 @@
     python tools/attn_stats.py [--json PATH] [--quick]
 
 The kernel measured is the instance the DiT launches 59 times per step — svi_attention_vt_fwd(q pre-scaled by softmax_scale*log2e, K token-major, V^T) at
-[L = 32760, 12 heads x 128] = flash_fwd2_kernel<0, 0, false, 1> (optimistic pass) + <.., 2> (flagged second pass) — timed with HIP events on the launch stream.
+[L = 32760, 12 heads x 128] = flash_fwd2_kernel<0, false, 1, false> (optimistic pass) + <.., 2> (flagged second pass) — timed with HIP events on the launch stream.
 
 Part A, "power or issue": the SAME binary on zero / small-magnitude / unit-Gaussian operands.  The instruction stream is identical (no data-dependent
 branch in the optimistic pass), so any difference in ms per launch is the part's clock under its power limit (MI355X_MICROARCH.md "DVFS give-back").  The

@@ -125,8 +125,10 @@ svi_status svi_dit_forward(svi_dit* h, const void* x, const float* timestep, con
  * (models/wan_video_dit.py:486-567): the audio windows are projected to 32 context tokens of width 768 per latent frame
  * (AudioProjModel, dit:44-115) and every block adds, after its text cross-attention,
  *     x += proj(attention_per_frame(q_linear(norm_x(x)), kv_linear(audio tokens of the frame)))     (dit:361-366, models/attention.py:318-371)
- * svi_dit_set_audio arms the handle for the following forwards (svi_dit_forward / _forward_tea; the CFG pair and the sequence-parallel
- * entry points refuse while audio is set) and NULL pointers disarm it:
+ * svi_dit_set_audio arms the handle for the following forwards (svi_dit_forward / _forward_tea, and sequence shards: svi_dit_sp_begin projects
+ * the audio tokens of ALL latent frames on every rank, and a shard's rows — which may start and end inside a frame — attend to their own frames'
+ * tokens through svi_attention_frames_fwd's kernel, the single-rank bits; the CFG pair, svi_dit_forward_cfg_pair and svi_dit_sp_begin_pair, refuses
+ * while audio is set: its branches differ in their audio) and NULL pointers disarm it:
  *   audio_first  bf16 [1, seq_len = 5, 12, 768]          the first frame's audio window          (audio_embed_tuple[0])
  *   audio_latter bf16 [T - 1, seq_len_vf = 8, 12, 768]   the later latent frames' windows        (audio_embed_tuple[1])
  * The pointers are borrowed until the next svi_dit_set_audio. */
@@ -182,7 +184,8 @@ svi_status svi_dit_context_refill(svi_dit* h, const void* context, const void* c
  *   svi_dit_sp_block_rest   attn bf16 [nrows, dim] (after the exchange back) -> output projection + gate + residual,
  *                           cross-attention, MLP of block `layer`
  *   svi_dit_sp_head         head rows bf16 [nrows, svi_dit_head_ld]; all-gathered, then svi_dit_unpatchify -> [out_dim, T, H, W]
- * With one rank (row0 = 0, nrows = L) the sequence is bit-identical to svi_dit_forward. */
+ * With one rank (row0 = 0, nrows = L) the sequence is bit-identical to svi_dit_forward.  With audio armed (svi_dit_set_audio) the talk variant runs on
+ * the shard: the windows must cover the whole sequence's T / patch_t latent frames, as on one rank. */
 svi_status svi_dit_sp_begin(svi_dit* h, const void* x, const float* timestep, const void* context, const void* clip_feature,
                             const void* y, const void* add_condition, int32_t T, int32_t H, int32_t W, int32_t Lc,
                             int32_t row0, int32_t nrows, svi_stream stream);
@@ -224,6 +227,13 @@ int64_t svi_dit_generation(svi_dit* h);
 svi_status svi_stream_buffers_release(svi_stream stream, int32_t all_streams);
 svi_status svi_attention_vt_fwd(const void* q, int32_t ldq, const void* k, int32_t ldk, const void* vt, int32_t ldvt, void* out,
                                 int32_t ldo, int32_t s_q, int32_t s_kv, int32_t n, int32_t q_prescaled, svi_stream stream);
+/* Frame-segmented attention (the talk variant's audio cross-attention, models/attention.py:318-371: a block-diagonal mask over frames) in ONE launch:
+ * q / out hold nrows rows, rows [row0, row0 + nrows) of a sequence of frames of rows_per_frame rows (q points at row row0); the rows of frame fr attend
+ * to keys [fr * keys_per_frame, (fr + 1) * keys_per_frame) of k [frames * keys_per_frame, ldk] and of vt [n*128, ldvt] (V transposed; both point at
+ * frame 0's keys; ldvt >= keys of every frame the range touches); scale head_dim^-0.5 on q as it is.  keys_per_frame % 8 == 0.  A range may start
+ * and end inside a frame.  Per row the same bits as svi_attention_vt_fwd(q_prescaled = 0) launched once per frame segment of the range. */
+svi_status svi_attention_frames_fwd(const void* q, int32_t ldq, const void* k, int32_t ldk, const void* vt, int32_t ldvt, void* out, int32_t ldo,
+                                    int32_t row0, int32_t nrows, int32_t rows_per_frame, int32_t keys_per_frame, int32_t n, svi_stream stream);
 
 /* CrossAttention.forward's query path (models/wan_video_dit.py:296,299: q = norm_q(self.q(x)); x = attn(q, k, v)) as the DiT block runs it by default:
  *   svi_linear_row_stats    C = bf16(A W^T + bias) [M, N] AND the statistic of RMSNorm over the full width (dit:192-197): row_sumsq [N/64][ldss] = sums of

@@ -364,6 +364,16 @@ extern "C" svi_status svi_attention_vt_fwd(const void* q, int32_t ldq, const voi
                             reinterpret_cast<bf16*>(out), ldo, s_q, s_kv, n, q_prescaled ? 1 : 0, st);
 }
 
+// The talk variant's per-frame attention over a row range of a frame-structured sequence, in one launch (svi_launch_flash_frames).
+extern "C" svi_status svi_attention_frames_fwd(const void* q, int32_t ldq, const void* k, int32_t ldk, const void* vt, int32_t ldvt, void* out,
+                                               int32_t ldo, int32_t row0, int32_t nrows, int32_t rows_per_frame, int32_t keys_per_frame,
+                                               int32_t n, svi_stream stream) {
+    SVI_REQUIRE(q && k && vt && out, "svi_attention_frames_fwd: null argument");
+    SVI_REQUIRE(n > 0 && ldq >= n * 128 && ldk >= n * 128 && ldo >= n * 128, "svi_attention_frames_fwd: bad sizes");
+    return svi_launch_flash_frames(reinterpret_cast<const bf16*>(q), ldq, reinterpret_cast<const bf16*>(k), ldk, reinterpret_cast<const bf16*>(vt), ldvt,
+                                   reinterpret_cast<bf16*>(out), ldo, row0, nrows, rows_per_frame, keys_per_frame, n, reinterpret_cast<hipStream_t>(stream));
+}
+
 extern "C" svi_status svi_video_to_u8(const float* video, uint8_t* frames, int32_t T, int32_t H, int32_t W, svi_stream stream) {
     SVI_REQUIRE(video && frames && T > 0 && H > 0 && W > 0, "svi_video_to_u8: bad argument");
     return svi_launch_video_to_u8(video, frames, (long)T * H * W, reinterpret_cast<hipStream_t>(stream));

@@ -56,15 +56,34 @@ __device__ __forceinline__ int perm23(int i) { return (i & 0x13) | ((i & 4) << 1
 //     separate normalisation pass (one more [L, D] read + write per block and branch) does not exist.
 #define CR_KEYS 128       // flash_cross_resident_kernel holds up to this many keys of one head in LDS
 #define CQ_LD 272         // bytes per row of the staged output tile (256 + 16: 16-byte aligned rows, rows 16 apart share a bank pair at worst)
-template <int TAG, int STAGED = 0>
+// FRAMES (the talk variant's audio attention, svi_launch_flash_frames): Q / O hold rows [seg_row0, seg_row0 + Lq) of a sequence made of frames of
+// seg_rpf rows; frame fr's rows attend to ITS keys only, rows fr * seg_kpf .. of K and the same columns of V^T (Lk_full = seg_kpf) — the block-diagonal
+// mask of models/attention.py:318-371 as one launch.  blockIdx.x enumerates (frame segment, 128-row tile of the segment): every segment has
+// ceil(seg_rpf / 128) tile slots, a tile starts at its segment's first row plus a multiple of 128 and ends with it, and the slots a cut segment (the
+// range's first and last) does not need return at once.  The map is arithmetic on the launch's arguments: no table, nothing read back.  Per row the
+// arithmetic is the plain kernel's (one query per lane column of S^T), and the tiles are those of one plain launch per segment — the same bits.
+template <int TAG, int STAGED = 0, bool FRAMES = false>
 __global__ __launch_bounds__(256, 2) void flash_fwd_kernel(const bf16* __restrict__ Q, int ldq,
                                                            const bf16* __restrict__ K, int ldk,
                                                            const bf16* __restrict__ VT, int ldvt,
                                                            bf16* __restrict__ O, int ldo, int Lq, int Lk_full,
                                                            float scale_log2e, const int* __restrict__ key_tail,
                                                            const float* __restrict__ q_rs = nullptr, const bf16* __restrict__ q_gain = nullptr, float q_out_scale = 1.0f,
-                                                           int long_keys_only = 0) {
+                                                           int long_keys_only = 0, int seg_row0 = 0, int seg_rpf = 1, int seg_kpf = 0) {
+    static_assert(!FRAMES || STAGED == 0, "the frame-segmented mode is a mode of the plain short-key kernel");
     extern __shared__ __attribute__((aligned(16))) char smem[];
+    int row_base = (STAGED ? blockIdx.y : blockIdx.x) * QB;
+    if constexpr (FRAMES) {
+        const int slots = (seg_rpf + QB - 1) / QB;
+        const int seg = blockIdx.x / slots, fr = seg_row0 / seg_rpf + seg;
+        const int first = max(fr * seg_rpf - seg_row0, 0);           // the segment's rows, relative to Q's first row
+        const int end = min((fr + 1) * seg_rpf - seg_row0, Lq);
+        row_base = first + (blockIdx.x - seg * slots) * QB;
+        if (row_base >= end) return;                                  // a slot the cut segment does not need (the whole workgroup)
+        Lq = end;                                                     // rows at or beyond the segment's end belong to the next frame
+        K += (size_t)fr * seg_kpf * ldk;
+        VT += (size_t)fr * seg_kpf;
+    }
     // key_tail = {n, m}: keys n-1 .. Lk_full-1 are identical (the caller's statement), so the softmax over all Lk_full keys equals the
     // softmax over keys 0 .. n-1 with key n-1 counted m times, i.e. with log2(m) added to its score in the exponent's units
     const int Lk = key_tail ? min(max(key_tail[0], 1), Lk_full) : Lk_full;
@@ -73,7 +92,6 @@ __global__ __launch_bounds__(256, 2) void flash_fwd_kernel(const bf16* __restric
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l31 = lane & 31, hi = lane >> 5;
     const int head = STAGED ? blockIdx.x : blockIdx.y;
-    const int row_base = (STAGED ? blockIdx.y : blockIdx.x) * QB;
     const int q_row = row_base + wave * 32 + l31;
     const bool q_ok = q_row < Lq;
 
@@ -2244,6 +2262,41 @@ svi_status svi_launch_flash(const bf16* Q, int ldq, const bf16* K, int ldk, cons
         hipLaunchKernelGGL(flash_fwd_kernel<0>, grid, block, lds, st, Q, ldq, K, ldk, VT, ldvt, O, ldo, Lq, Lk, v1_scale, key_tail);
     else
         hipLaunchKernelGGL(flash_fwd_kernel<1>, grid, block, lds, st, Q, ldq, K, ldk, VT, ldvt, O, ldo, Lq, Lk, v1_scale, key_tail);
+    SVI_LAUNCH_CHECK();
+    return SVI_OK;
+}
+
+svi_status svi_launch_flash_frames(const bf16* Q, int ldq, const bf16* K, int ldk, const bf16* VT, int ldvt, bf16* O, int ldo, int row0, int nrows,
+                                   int rows_per_frame, int keys_per_frame, int num_heads, hipStream_t st) {
+    SVI_REQUIRE(row0 >= 0 && nrows > 0 && rows_per_frame > 0 && keys_per_frame > 0 && num_heads > 0 && num_heads <= 65535,
+                "frame attention: bad sizes row0=%d nrows=%d rows_per_frame=%d keys_per_frame=%d heads=%d", row0, nrows, rows_per_frame, keys_per_frame, num_heads);
+    SVI_REQUIRE(keys_per_frame % 8 == 0, "frame attention: keys per frame (%d) must be a multiple of 8 (a frame's V^T columns start 16-byte aligned)", keys_per_frame);
+    SVI_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ldvt % 8 == 0 && ldo % 4 == 0, "frame attention: leading dims must be multiples of 8");
+    SVI_REQUIRE(((uintptr_t)Q % 16) == 0 && ((uintptr_t)K % 16) == 0 && ((uintptr_t)VT % 16) == 0 && ((uintptr_t)O % 8) == 0, "frame attention: operands must be 16-byte aligned");
+    const int fr0 = row0 / rows_per_frame, fr1 = (int)(((long)row0 + nrows - 1) / rows_per_frame);
+    SVI_REQUIRE((long)(fr1 + 1) * keys_per_frame <= ldvt, "frame attention: V^T leading dim %d < the %ld keys of frames 0 .. %d", ldvt, (long)(fr1 + 1) * keys_per_frame, fr1);
+    SVI_REQUIRE((long)row0 + nrows < (1L << 31) && (long)(fr1 + 1) * rows_per_frame < (1L << 31), "frame attention: row indices of 2^31 or more");
+    int ncu = 256, kernel = 0;
+    SVI_TRY((svi_status)flash_device_cus(&ncu));
+    (void)svi_flash_plan(rows_per_frame, keys_per_frame, num_heads, ncu, &kernel);
+    if (kernel != 1) {
+        // the launch plan gives this shape to the long-sequence kernel (SVI_FLASH_KERNEL = 2, or >= 2048 keys per frame): one launch per segment, as
+        // the per-frame loop this replaces made them
+        for (int fr = fr0; fr <= fr1; ++fr) {
+            const int a = std::max(fr * rows_per_frame, row0) - row0, b = std::min((fr + 1) * rows_per_frame, row0 + nrows) - row0;
+            SVI_TRY(svi_launch_flash(Q + (size_t)a * ldq, ldq, K + (size_t)fr * keys_per_frame * ldk, ldk, VT + (size_t)fr * keys_per_frame, ldvt,
+                                     O + (size_t)a * ldo, ldo, b - a, keys_per_frame, num_heads, 0, st));
+        }
+        return SVI_OK;
+    }
+    const int lds = 2 * (KT_BYTES + VT_BYTES);
+    SVI_TRY(svi_ensure_lds(reinterpret_cast<const void*>(flash_fwd_kernel<1, 0, true>), lds));
+    const long slots = (long)(fr1 - fr0 + 1) * ((rows_per_frame + QB - 1) / QB);
+    SVI_REQUIRE(slots < (1L << 31), "frame attention: %ld workgroups per head", slots);
+    dim3 grid((unsigned)slots, num_heads), block(256);
+    const float scale_log2e = 1.4426950408889634f / sqrtf((float)DH);       // head_dim^-0.5 on q as it is (svi_launch_flash with q_prescaled = 0)
+    hipLaunchKernelGGL((flash_fwd_kernel<1, 0, true>), grid, block, lds, st, Q, ldq, K, ldk, VT, ldvt, O, ldo, nrows, keys_per_frame, scale_log2e,
+                       (const int*)nullptr, (const float*)nullptr, (const bf16*)nullptr, 1.0f, 0, row0, rows_per_frame, keys_per_frame);
     SVI_LAUNCH_CHECK();
     return SVI_OK;
 }

@@ -248,6 +248,12 @@ svi_status svi_launch_gemm_mx8_wscaled(const SviGemmArgs& g, const unsigned* w_s
 struct SviQk8 { unsigned char* q8; unsigned char* k8; unsigned* qs; unsigned* ks; int ld8, qs_rows, ks_rows; };
 svi_status svi_launch_flash(const bf16* Q, int ldq, const bf16* K, int ldk, const bf16* VT, int ldvt,
                             bf16* O, int ldo, int Lq, int Lk, int num_heads, int q_prescaled, hipStream_t st, const int* key_tail = nullptr, const SviQk8* qk8 = nullptr);
+// Frame-segmented short-key attention (the talk variant's audio cross-attention, models/attention.py:318-371): Q / O point at row row0 of a sequence of
+// frames of rows_per_frame rows and hold nrows rows; the rows of frame fr attend to keys [fr * keys_per_frame, (fr + 1) * keys_per_frame) of K and V^T
+// (K / VT point at frame 0's keys), scale head_dim^-0.5 on q as it is.  One launch of flash_fwd_kernel's FRAMES mode: per row the same bits as one
+// svi_launch_flash(q_prescaled = 0) per frame segment of the range.  keys_per_frame % 8 == 0.
+svi_status svi_launch_flash_frames(const bf16* Q, int ldq, const bf16* K, int ldk, const bf16* VT, int ldvt, bf16* O, int ldo, int row0, int nrows,
+                                   int rows_per_frame, int keys_per_frame, int num_heads, hipStream_t st);
 // Cross-attention over a SHORT key axis (the prompt: <= 512 keys, a few dozen distinct) with the query's RMSNorm applied as the rows are read:
 //   q' = bf16(bf16(bf16(q * rs[row]) * gain) * out_scale)      — RMSNorm.forward's rounding points (dit:192-197) and the scale folded in as svi_launch_rmsnorm_rope does
 // Q holds the RAW projection output; rs[row] = rsqrt(mean(q^2) + eps) from svi_launch_row_rs; norm == nullptr: Q is used as it is (pre-scaled).

@@ -124,6 +124,7 @@ struct svi_dit {
     // sequence-parallel shard in flight (svi_dit_sp_begin .. svi_dit_sp_head)
     int sp_rows = 0, sp_row0 = 0, sp_Lc = 0;
     int sp_nb = 1;                    // 2: the shard carries both CFG branches stacked (svi_dit_sp_begin_pair): X = [cond rows | uncond rows]
+    int sp_aud_frames = 0, sp_aud_rpf = 0;     // talk variant on the shard: latent frames of the WHOLE sequence (0: no audio), rows per frame
     bool sp_active = false;
     const bf16* sp_ctxp = nullptr;
     const bf16* sp_ctxp_b = nullptr;
@@ -650,9 +651,10 @@ static svi_status fill_block_kv(svi_dit* h, int layer, const bf16* CTX, int Lc, 
 // Cross-attention and MLP thirds of a block.
 // nb > 1: X holds nb samples stacked (nb * L rows); sample s attends to its own context (CTXs[s], kvs[s]) — the conditional and the
 // unconditional prompt of a CFG step.  Row-local work (norms, projections, MLP) runs once over all rows.
-static svi_status block_audio(svi_dit* h, int layer, bf16* X, int L, int f, hipStream_t st);
+// audio_frames > 0 (talk variant): X holds rows [audio_row0, audio_row0 + L) of a sequence of audio_frames frames of audio_rpf rows each (one rank: 0, L / f).
+static svi_status block_audio(svi_dit* h, int layer, bf16* X, int L, int f, int row0, int rpf, hipStream_t st);
 static svi_status run_block_rest_n(svi_dit* h, int layer, bf16* X, const bf16* const* CTXs, const float* modf, int L, int Lc,
-                                   const CtxKV* kvs, int nb, hipStream_t st, int audio_frames = 0) {
+                                   const CtxKV* kvs, int nb, hipStream_t st, int audio_frames = 0, int audio_row0 = 0, int audio_rpf = 0) {
     const svi_dit_config& c = h->cfg;
     const BlockW& b = h->blocks[layer];
     Workspace& w = h->ws;
@@ -700,7 +702,7 @@ static svi_status run_block_rest_n(svi_dit* h, int layer, bf16* X, const bf16* c
     if (proj_mx8_on(h)) { SviProfScope _p(PROF_GEMM_CROSS, st); SVI_TRY(linear_mx8(h, w.Hb, true, b.proj_8[5], b.ca.o.b, X, D, R, SVI_EPI_BIAS_GATE_RES, st, nullptr, X, D)); }
     else { SviProfScope _p(PROF_GEMM_CROSS, st); SVI_TRY(linear(w.Hb, D, b.ca.o, X, D, R, D, D, SVI_EPI_BIAS_GATE_RES, st, nullptr, X, D, nb)); }
     // --- talk variant: audio cross-attention between the text cross-attention and the MLP (dit:361-366)
-    if (audio_frames > 0) SVI_TRY(block_audio(h, layer, X, L, audio_frames, st));
+    if (audio_frames > 0) SVI_TRY(block_audio(h, layer, X, L, audio_frames, audio_row0, audio_rpf, st));
     // --- MLP: x += gate_mlp * W2 gelu_tanh(W1 modulate(norm2 x))                  dit:372-373,334-335
     { SviProfScope _p(PROF_LN, st); SVI_TRY(svi_launch_ln_mod(X, D, w.Hb, D, R, D, c.eps, nullptr, nullptr, sh_m, sc_m, st)); }
     if (h->ffn_mx8) {          // opt-in MX-fp8 MLP: both GEMMs on v_mfma_scale_f32_32x32x64_f8f6f4, activations quantised per 32-element K block
@@ -742,14 +744,14 @@ static svi_status run_block_rest_n(svi_dit* h, int layer, bf16* X, const bf16* c
     return SVI_OK;
 }
 static svi_status run_block_rest(svi_dit* h, int layer, bf16* X, const bf16* CTX, const float* modf, int L, int Lc,
-                                 const CtxKV& kv, hipStream_t st, int audio_frames = 0) {
-    return run_block_rest_n(h, layer, X, &CTX, modf, L, Lc, &kv, 1, st, audio_frames);
+                                 const CtxKV& kv, hipStream_t st, int audio_frames = 0, int audio_row0 = 0, int audio_rpf = 0) {
+    return run_block_rest_n(h, layer, X, &CTX, modf, L, Lc, &kv, 1, st, audio_frames, audio_row0, audio_rpf);
 }
 
 static svi_status run_block(svi_dit* h, int layer, bf16* X, const bf16* CTX, const float* modf, int L, int Lc,
                             const CtxKV& kv, hipStream_t st, int audio_frames = 0) {
     SVI_TRY(run_block_self(h, layer, X, modf, L, st));
-    return run_block_rest(h, layer, X, CTX, modf, L, Lc, kv, st, audio_frames);
+    return run_block_rest(h, layer, X, CTX, modf, L, Lc, kv, st, audio_frames, 0, audio_frames ? L / audio_frames : 0);
 }
 
 // ---- talk variant ---------------------------------------------------------------------------------------------------------------
@@ -789,19 +791,20 @@ static svi_status stage_audio(svi_dit* h, int f, hipStream_t st) {
 // x += proj(attention_per_frame(q_linear(norm_x(x)), kv_linear(audio)))   (DiTBlock.forward dit:361-366; SingleStreamAttention.forward,
 // models/attention.py:318-371 with human_num == 1): frame fr's h*w tokens attend to that frame's 32 audio tokens, scale head_dim^-0.5,
 // no q/k norm, no RoPE.  K | V of the audio tokens depend on (audio, weights) only; they are re-projected per forward (3 GFLOP per block).
-static svi_status block_audio(svi_dit* h, int layer, bf16* X, int L, int f, hipStream_t st) {
+// X holds rows [row0, row0 + L) of the f * rpf-row sequence (a sequence-parallel shard cuts frames anywhere); K | V cover all f frames, so one
+// frame-segmented attention launch serves any range with the bits of one launch per frame.
+static svi_status block_audio(svi_dit* h, int layer, bf16* X, int L, int f, int row0, int rpf, hipStream_t st) {
     const svi_dit_config& c = h->cfg;
     const BlockW& b = h->blocks[layer];
     Workspace& w = h->ws;
-    const int D = c.dim, na = f * SVI_AUD_TOK, S = L / f;
+    const int D = c.dim, na = f * SVI_AUD_TOK;
+    SVI_REQUIRE(rpf > 0 && row0 >= 0 && (long)row0 + L <= (long)f * rpf, "audio attention: rows [%d, %d) outside %d frames of %d rows", row0, row0 + L, f, rpf);
     const Lin lk{b.aud_kv.w, b.aud_kv.b}, lv{b.aud_kv.w + (size_t)D * SVI_AUD_DIM, b.aud_kv.b + D};      // kv_linear rows [0, D) = K, [D, 2D) = V
     SVI_TRY(svi_launch_ln_mod(X, D, w.Hb, D, L, D, c.eps, b.normx_w, b.normx_b, nullptr, nullptr, st));
     SVI_TRY(linear(w.Hb, D, b.aud_q, w.QK, 2 * D, L, D, D, SVI_EPI_BIAS, st));
     SVI_TRY(linear(h->AUD, SVI_AUD_DIM, lk, h->AK, D, na, D, SVI_AUD_DIM, SVI_EPI_BIAS, st));
     SVI_TRY(linear_transposed(h->AUD, SVI_AUD_DIM, lv, h->AVT, h->ldavt, na, D, SVI_AUD_DIM, st));
-    for (int fr = 0; fr < f; ++fr)
-        SVI_TRY(svi_launch_flash(w.QK + (size_t)fr * S * 2 * D, 2 * D, h->AK + (size_t)fr * SVI_AUD_TOK * D, D, h->AVT + (size_t)fr * SVI_AUD_TOK, h->ldavt,
-                                 w.Hb + (size_t)fr * S * D, D, S, SVI_AUD_TOK, c.num_heads, 0, st));
+    SVI_TRY(svi_launch_flash_frames(w.QK, 2 * D, h->AK, D, h->AVT, h->ldavt, w.Hb, D, row0, L, rpf, SVI_AUD_TOK, c.num_heads, st));
     return linear(w.Hb, D, b.aud_proj, X, D, L, D, D, SVI_EPI_BIAS_GATE_RES, st, nullptr, X, D);
 }
 
@@ -1249,7 +1252,6 @@ extern "C" svi_status svi_dit_sp_begin(svi_dit* h, const void* x, const float* t
     SVI_REQUIRE_DEVICE(h);
     const svi_dit_config& c = h->cfg;
     SVI_REQUIRE(T > 0 && H > 0 && W > 0 && Lc > 0 && T % c.patch_t == 0 && H % c.patch_h == 0 && W % c.patch_w == 0, "svi_dit_sp_begin: bad sizes");
-    if (h->aud_first) { svi_set_error("svi_dit_sp_begin: the talk variant's per-frame audio attention is not served on sequence shards"); return SVI_ERR_UNSUPPORTED; }
     SVI_REQUIRE(y || c.in_dim == 16, "this model takes %d extra input channels: y must be given", c.in_dim - 16);
     SVI_REQUIRE(!c.has_image_input || clip_feature, "has_image_input model needs clip_feature");
     const int f = T / c.patch_t, hh = H / c.patch_h, ww = W / c.patch_w, L = f * hh * ww;
@@ -1264,6 +1266,11 @@ extern "C" svi_status svi_dit_sp_begin(svi_dit* h, const void* x, const float* t
                           reinterpret_cast<const bf16*>(y), Lc, &cu, st));
     SVI_TRY(stage_embed(h, reinterpret_cast<const bf16*>(x), reinterpret_cast<const bf16*>(y), reinterpret_cast<const bf16*>(add_condition),
                         T, H, W, nrows, st, row0));
+    // talk variant armed: every rank projects the audio tokens of ALL f latent frames (a few GFLOP, replicated) — a shard's rows may belong to any
+    // frames, and the windows are checked against the whole sequence's frame count
+    const int audio_frames = h->aud_first ? f : 0;
+    if (audio_frames) SVI_TRY(stage_audio(h, f, st));
+    h->sp_aud_frames = audio_frames; h->sp_aud_rpf = hh * ww;
     h->sp_rows = nrows; h->sp_row0 = row0; h->sp_Lc = Lc; h->sp_active = true; h->sp_ctxp = cu.CTXp; h->sp_nb = 1;
     h->sp_kv.clear();
     for (int l = 0; l < c.num_layers; ++l) h->sp_kv.push_back(kv_of(h, cu, l));
@@ -1283,7 +1290,7 @@ extern "C" svi_status svi_dit_sp_begin_pair(svi_dit* h, const void* x, const flo
     const svi_dit_config& c = h->cfg;
     SVI_REQUIRE(h->ctx_cache_on, "svi_dit_sp_begin_pair: the stacked CFG pair needs the context cache (svi_dit_context_cache(h, 1))");
     SVI_REQUIRE(T > 0 && H > 0 && W > 0 && Lc > 0 && T % c.patch_t == 0 && H % c.patch_h == 0 && W % c.patch_w == 0, "svi_dit_sp_begin_pair: bad sizes");
-    if (h->aud_first) { svi_set_error("svi_dit_sp_begin_pair: the talk variant's per-frame audio attention is not served on sequence shards"); return SVI_ERR_UNSUPPORTED; }
+    if (h->aud_first) { svi_set_error("svi_dit_sp_begin_pair: the talk variant's branches differ in their audio; run them as separate shard forwards (svi_dit_sp_begin)"); return SVI_ERR_UNSUPPORTED; }
     SVI_REQUIRE(y || c.in_dim == 16, "this model takes %d extra input channels: y must be given", c.in_dim - 16);
     SVI_REQUIRE(!c.has_image_input || clip_feature, "has_image_input model needs clip_feature");
     const int f = T / c.patch_t, hh = H / c.patch_h, ww = W / c.patch_w, L = f * hh * ww;
@@ -1366,7 +1373,7 @@ extern "C" svi_status svi_dit_sp_block_rest(svi_dit* h, int32_t layer, const voi
         return run_block_rest_n(h, layer, h->ws.X, CTXs, modf, h->sp_rows, h->sp_Lc, kvs, 2, st);
     }
     SVI_TRY(block_attn_out(h, layer, h->ws.X, reinterpret_cast<const bf16*>(attn), modf, h->sp_rows, st));
-    return run_block_rest(h, layer, h->ws.X, h->sp_ctxp, modf, h->sp_rows, h->sp_Lc, h->sp_kv[layer], st);
+    return run_block_rest(h, layer, h->ws.X, h->sp_ctxp, modf, h->sp_rows, h->sp_Lc, h->sp_kv[layer], st, h->sp_aud_frames, h->sp_row0, h->sp_aud_rpf);
 }
 
 extern "C" svi_status svi_dit_sp_head(svi_dit* h, void* head_rows_out, svi_stream stream) {

@@ -61,6 +61,7 @@ SYMBOLS = [
     ("svi_stream_buffers_release", _i32, [_vp, _i32]),
     ("svi_attention_last_flagged", _i32, [_vp, C.POINTER(_i32), C.POINTER(_i32)]),
     ("svi_attention_vt_fwd", _i32, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
+    ("svi_attention_frames_fwd", _i32, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     ("svi_dit_set_audio", _i32, [_vp, _vp, _vp, _i32]),
     ("svi_cfg3_step", _i32, [_vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _vp]),
     ("svi_dit_time_mod", _i32, [_vp, _vp, _vp, _i32, _vp]),

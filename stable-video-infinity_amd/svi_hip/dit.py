@@ -477,18 +477,18 @@ def model_fn_wan_talk_video(dit: WanDiT, x: torch.Tensor, timestep: torch.Tensor
                             add_condition=None, audio_embed_tuple=None, use_unified_sequence_parallel: bool = False,
                             use_controlnet: bool = False, **kwargs) -> torch.Tensor:
     """Same signature as pipelines/svi_video_talk.py:83-96.  The audio windows arm the per-block audio cross-attention for this call
-    (WanDiT.set_audio); everything else is model_fn_wan_video.  Not served: use_controlnet (blocks that also return add_condition) and
-    sequence parallelism together with audio."""
+    (WanDiT.set_audio); everything else is model_fn_wan_video — including use_unified_sequence_parallel: on shards every rank projects all
+    frames' audio tokens and its rows attend to their own frames' tokens (the reference's block-diagonal mask, models/attention.py:318-371),
+    with the single-rank bits; TeaCache residuals cover the rank's rows.  Not served: use_controlnet (blocks that also return add_condition)."""
     if use_controlnet:
         raise NotImplementedError("the talk variant's controlnet blocks are not served by the HIP backend")
     if audio_embed_tuple is None:
         raise ValueError("model_fn_wan_talk_video needs audio_embed_tuple (the reference dereferences it unconditionally, svi_video_talk.py:126)")
-    if use_unified_sequence_parallel:
-        import torch.distributed as dist
-        if dist.is_available() and dist.is_initialized() and dist.get_world_size(getattr(dit, "sp_group", None)) > 1:
-            raise NotImplementedError("the talk variant's per-frame audio attention is not served on sequence shards")
     dit.set_audio(audio_embed_tuple)
     try:
-        return model_fn_wan_video(dit, x, timestep, context, clip_feature=clip_feature, y=y, tea_cache=tea_cache, add_condition=add_condition)
+        if dit._audio[1].shape[1] != x.shape[2] - 1:           # before any collective: the same answer on every rank
+            raise ValueError(f"audio windows cover {dit._audio[1].shape[1] + 1} latent frames, the latents have {x.shape[2]}")
+        return model_fn_wan_video(dit, x, timestep, context, clip_feature=clip_feature, y=y, tea_cache=tea_cache, add_condition=add_condition,
+                                  use_unified_sequence_parallel=use_unified_sequence_parallel)
     finally:
         dit.set_audio(None)

@@ -159,6 +159,19 @@ def linear_row_stats(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch
     return y, rs, ss
 
 
+def frame_attention(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, num_heads: int, rows_per_frame: int, keys_per_frame: int = 32,
+                    row0: int = 0) -> torch.Tensor:
+    """The talk variant's per-frame attention (models/attention.py:318-371, a block-diagonal mask over frames) in one launch
+    (svi_attention_frames_fwd): q bf16 [nrows, n*128] = rows [row0, row0 + nrows) of a sequence of frames of `rows_per_frame` rows; the rows of
+    frame fr attend to keys [fr * keys_per_frame, (fr + 1) * keys_per_frame) of k bf16 [frames * keys_per_frame, n*128] and of vt bf16 [n*128, ldvt]
+    (V transposed); scale head_dim^-0.5.  Returns [nrows, n*128]."""
+    q, k, vt = _chk(q, "q"), _chk(k, "k"), _chk(vt, "vt")
+    out = torch.empty((q.shape[0], num_heads * 128), dtype=torch.bfloat16, device=q.device)
+    L.check(L.lib().svi_attention_frames_fwd(L.ptr(q), q.shape[1], L.ptr(k), k.shape[1], L.ptr(vt), vt.shape[1], L.ptr(out), out.shape[1], int(row0),
+                                             q.shape[0], int(rows_per_frame), int(keys_per_frame), num_heads, L.current_stream()), "frame_attention")
+    return out
+
+
 def cross_attention(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, num_heads: int, s_kv: Optional[int] = None, q_rs: Optional[torch.Tensor] = None,
                     q_gain: Optional[torch.Tensor] = None, q_out_scale: float = 1.0, key_tail: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The DiT block's cross-attention over the prompt's (short) key axis (svi_cross_attention_fwd): q bf16 [Lq, n*128] — with q_rs / q_gain the RAW

@@ -294,8 +294,14 @@ class DenoiseLoop:
                          denoising_strength: float = 1.0, progress_bar_cmd: Callable = lambda x: x, add_condition=None, **cond) -> torch.Tensor:
         """SVITalkVideoPipeline._sample_with_multitalk (svi_video_talk.py:448-463): per step three forwards — conditional (prompt, audio,
         add_condition), unconditional (negative prompt, null audio, no add_condition), drop-text (negative prompt, audio, add_condition) —
-        combined as uncond + text*(cond - drop_text) + audio*(drop_text - uncond); one forward when both scales are 1."""
-        from .dit import model_fn_wan_talk_video as fn
+        combined as uncond + text*(cond - drop_text) + audio*(drop_text - uncond); one forward when both scales are 1.
+        A loop built with sequence_parallel=True (+ sp_group) runs each of the three forwards on this rank's sequence shard
+        (model_fn_wan_talk_video with use_unified_sequence_parallel): every rank ends with the full noise predictions and the same latents."""
+        from .dit import model_fn_wan_talk_video
+        fn = model_fn_wan_talk_video
+        if self.sequence_parallel:
+            self.dit.sp_group = self.sp_group
+            fn = lambda *a, **kw: model_fn_wan_talk_video(*a, use_unified_sequence_parallel=True, **kw)      # noqa: E731
         self.scheduler.set_timesteps(num_inference_steps, denoising_strength=denoising_strength, shift=sigma_shift)
         latents = latents.to(torch.bfloat16).contiguous().clone()
         ts_dev = self.scheduler.timesteps.to(device=latents.device, dtype=torch.float32)

@@ -235,6 +235,8 @@ class SequenceShard:
             clip_feature = None
         x = self._setup(x, (context,), clip_feature, y, add_condition, 1)
         T, H, W = self.T, self.H, self.W
+        if d._audio is not None and d._audio[1].shape[1] != T - 1:      # the talk variant: windows of the WHOLE clip, as on one rank
+            raise ValueError(f"audio windows cover {d._audio[1].shape[1] + 1} latent frames, the latents have {T}")
         context, clip_feature = d._prompt_args(context, clip_feature)
         self._keep = [x, context, timestep.to(device=x.device, dtype=torch.float32).reshape(-1).contiguous(), clip_feature,
                       None if y is None else y.to(torch.bfloat16).contiguous(),
@@ -366,13 +368,36 @@ def _all_gather_into(out: torch.Tensor, mine: torch.Tensor, group, overlap: bool
     return dist.all_gather_into_tensor(out, mine.contiguous(), group=group, async_op=overlap)
 
 
+def _armed(dits: Sequence[WanDiT], audio_embed_tuple):
+    """Arm every handle with the talk variant's audio windows for one forward (None: leave whatever is armed); returns the disarm callback."""
+    if audio_embed_tuple is None:
+        return lambda: None
+    for d in dits:
+        d.set_audio(audio_embed_tuple)
+
+    def disarm():
+        for d in dits:
+            d.set_audio(None)
+    return disarm
+
+
 def forward_distributed(dit: WanDiT, x, timestep, context, group=None, groups: Optional[int] = None, tea_mode: int = 0,
-                        residual: Optional[torch.Tensor] = None, mode: Optional[str] = None, **cond) -> torch.Tensor:
+                        residual: Optional[torch.Tensor] = None, mode: Optional[str] = None, audio_embed_tuple=None, **cond) -> torch.Tensor:
     """model_fn_wan_video(..., use_unified_sequence_parallel=True) for this rank of `group`: every rank passes the same inputs
     and receives the full output.  Per block: the q | k | V^T exchange pipelined over G head groups against attention, the output
     exchange pipelined the same way; one all-gather per forward.
     tea_mode / residual (TeaCache, as WanDiT.forward): 1 = also write this rank's residual rows [Ls, dim]; 2 = skip the blocks and add
-    `residual` — no exchange at all in that forward besides the final all-gather."""
+    `residual` — no exchange at all in that forward besides the final all-gather.
+    audio_embed_tuple (the talk variant, WanDiT.set_audio): armed for this forward and disarmed after it; a handle armed beforehand
+    (model_fn_wan_talk_video) is served as it is.  Every rank projects all frames' audio tokens; its rows attend to their own frames'."""
+    disarm = _armed([dit], audio_embed_tuple)
+    try:
+        return _forward_distributed(dit, x, timestep, context, group, groups, tea_mode, residual, mode, **cond)
+    finally:
+        disarm()
+
+
+def _forward_distributed(dit: WanDiT, x, timestep, context, group, groups, tea_mode, residual, mode, **cond) -> torch.Tensor:
     rank, world = dist.get_rank(group), dist.get_world_size(group)
     sh = SequenceShard(dit, rank, world, groups, mode)
     sh.begin(x, timestep, context, **cond)
@@ -402,10 +427,20 @@ def forward_distributed(dit: WanDiT, x, timestep, context, group=None, groups: O
     return sh.unpatchify(all_gather_rows(sh.head(), group))
 
 
-def forward_local(dits: Sequence[WanDiT], x, timestep, context, groups: Optional[int] = None, mode: Optional[str] = None, **cond) -> torch.Tensor:
+def forward_local(dits: Sequence[WanDiT], x, timestep, context, groups: Optional[int] = None, mode: Optional[str] = None,
+                  audio_embed_tuple=None, **cond) -> torch.Tensor:
     """The same schedule with P = len(dits) shards in ONE process (each shard needs its own handle: a handle holds one
     workspace); the exchanges are device copies between the shards' buffers.  For tests and for measuring what the schedule costs
-    besides the transport on a single GPU (tools/sp_overhead.py)."""
+    besides the transport on a single GPU (tools/sp_overhead.py, tools/talk_sp_timing.py).  audio_embed_tuple: every shard's handle is armed
+    with the same windows for this forward (the talk variant) and disarmed after it."""
+    disarm = _armed(dits, audio_embed_tuple)
+    try:
+        return _forward_local(dits, x, timestep, context, groups, mode, **cond)
+    finally:
+        disarm()
+
+
+def _forward_local(dits: Sequence[WanDiT], x, timestep, context, groups, mode, **cond) -> torch.Tensor:
     P = len(dits)
     shards = [SequenceShard(d, r, P, groups, mode) for r, d in enumerate(dits)]
     for sh in shards:

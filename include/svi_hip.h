@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define SVI_HIP_ABI_VERSION 10
+#define SVI_HIP_ABI_VERSION 11
 
 typedef enum {
     SVI_OK = 0,
@@ -274,6 +274,15 @@ svi_status svi_attention_last_flagged(svi_stream stream, int32_t* flagged_out, i
  * the items of a partly filled last round are cut along the key axis (csrc/svi_attention.hip flash_splits). */
 svi_status svi_gemm_plan(int32_t M, int32_t N, int32_t K, int32_t epilogue, int32_t skinny, int32_t compute_units, int32_t* kernel_out);
 svi_status svi_attention_plan(int32_t s_q, int32_t s_kv, int32_t heads, int32_t compute_units, int32_t* out4);
+/* ABI v11 — the VAE's plane-fed residual-block convolution (3x3x3 over Cin -> Cout, stride 1, causal, 'same'; input [frames][Ho][Wo][Cin]):
+ * svi_vae_conv_plan: out8 = {kernel (0 = the layer does not take the producer's fp16 planes, 1 = conv_dma2h_kernel<1> (Cout <= 32), 3 = conv_dma2h_kernel<3>,
+ *   2 = conv_dma2h_pair_kernel: two 256-pixel tiles per workgroup), the tile order ord_T, ord_Lf, ord_G (frames x tiles per frame walked in groups of ord_G
+ *   tiles through all frames; ord_T = 0: pixel order), workgroups, the largest frame distance between the two tiles of one workgroup, the bytes the largest
+ *   activation descriptor must address (must stay below 0xFFE00000), the launch guard's bound on that ((kt + 3) frames)}.  Follows SVI_VAE_PAIR,
+ *   SVI_VAE_TILE_ORDER, SVI_VAE_DMA, SVI_VAE_X2H and SVI_VAE_EXACT_FP32 as the launcher does.
+ * svi_vae_tile_order: out[i] (ord_T x ord_Lf entries) = the frame-major pixel tile that launch position i computes under that order. */
+svi_status svi_vae_conv_plan(int32_t Cin, int32_t Cout, int32_t kt, int32_t frames, int32_t Ho, int32_t Wo, int64_t* out8);
+svi_status svi_vae_tile_order(int32_t ord_T, int32_t ord_Lf, int32_t ord_G, int64_t* out);
 
 /* nn.LayerNorm(eps) [+ affine w,b] [+ modulate(x, shift, scale)] over rows of x[rows, dim]
  * (models/wan_video_dit.py:150-151,331-333,358,372).  w,b,shift,scale are bf16 [dim] or NULL. */

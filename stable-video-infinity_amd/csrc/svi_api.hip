@@ -507,6 +507,12 @@ extern "C" svi_status svi_attention_plan(int32_t s_q, int32_t s_kv, int32_t head
     out4[0] = kernel; out4[1] = sp.whole; out4[2] = sp.pieces; out4[3] = sp.whole + (items - sp.whole) * sp.pieces;
     return SVI_OK;
 }
+extern "C" svi_status svi_vae_conv_plan(int32_t Cin, int32_t Cout, int32_t kt, int32_t frames, int32_t Ho, int32_t Wo, int64_t* out8) {
+    return svi_vae_conv_choose(Cin, Cout, kt, frames, Ho, Wo, out8);
+}
+extern "C" svi_status svi_vae_tile_order(int32_t ord_T, int32_t ord_Lf, int32_t ord_G, int64_t* out) {
+    return svi_vae_tile_order_fill(ord_T, ord_Lf, ord_G, out);
+}
 
 // MX-fp8 operator seams (opt-in path; see csrc/svi_gemm.hip): quantise bf16 activations, and the block-scaled GEMM itself.
 extern "C" svi_status svi_mx8_quantize(const void* x, int32_t ldx, int32_t rows, int32_t K, void* q, int32_t ldq, void* scales, int32_t sc_rows,

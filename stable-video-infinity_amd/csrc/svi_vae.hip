@@ -656,6 +656,20 @@ __global__ __launch_bounds__(512, 2) void conv_igemm_x3_kernel(ConvP p) {
 // residual-block convolution.  LDS: two stages x (2 x [272][64 B] + 3 taps x 2 x [96][64 B]) = 140 KiB.
 // =================================================================================================
 #define D2_ROWS 272
+// Launch position `tile` -> pixel tile of the plane-fed convolutions (conv_dma2h_kernel, conv_dma2h_pair_kernel; the host planner asks the same
+// function).  ord_T frames of ord_Lf tiles each: workgroups walk groups of ord_G tiles through ALL frames before moving down the image; the rest of
+// a frame (ord_Lf % ord_G tiles) forms a last, shorter group.  ord_T = 0: pixel order.  `tile` < ord_T x ord_Lf.
+__host__ __device__ __forceinline__ long conv_tile_at(int ord_T, int ord_Lf, int ord_G, long tile) {
+    if (ord_T <= 0) return tile;
+    const long per_group = (long)ord_T * ord_G;
+    const int full = ord_Lf / ord_G;                         // whole groups
+    const long g = tile / per_group;
+    int gl = ord_G;
+    long r = tile - g * per_group, gbase = g * ord_G;
+    if (g >= full) { gl = ord_Lf - full * ord_G; r = tile - (long)full * per_group; gbase = (long)full * ord_G; }
+    const int t = (int)(r / gl), j = (int)(r - (long)t * gl);
+    return (long)t * ord_Lf + gbase + j;
+}
 #define D2_A_PLANE (D2_ROWS * 64)
 #define D2_STAGE (2 * D2_A_PLANE + 6 * X3_W_PLANE)
 // NB: 32-output-channel blocks per workgroup.  3: the residual-block convolutions (Cout = 96 per grid.y).  1: narrow heads (Cout <= 32: the
@@ -680,22 +694,13 @@ __global__ __launch_bounds__(512, 2) void conv_dma2h_kernel(ConvP p) {
     // earlier frames a causal 3x3x3 convolution reads were last touched one and two whole frames ago (153 MB of planes per frame at
     // 480 x 832 x 96: out of L2, largely out of the 256 MB MALL).  With ord_T frames of ord_Lf tiles each, workgroups walk groups of ord_G tiles
     // (about 16 image rows) through ALL frames before moving down the image: the slab of input rows a group needs from frames t-2, t-1, t is
-    // reused while it is still close.
+    // reused while it is still close (conv_tile_at; launch_conv_planes picks ord_*).
     // Output-channel blocks of one pixel tile sit next to each other in the launch order (1-D grid: workgroup = tile * blocks + block), so the
     // 2 or 4 workgroups that read the same activation strips run together instead of a whole tensor apart.
     const int ncob = (p.Cout + NB * 32 - 1) / (NB * 32);
     long tile = blockIdx.x / ncob;
     const int cob = (int)(blockIdx.x - tile * ncob);
-    if (p.ord_T > 0) {
-        const long per_group = (long)p.ord_T * p.ord_G;
-        const int full = p.ord_Lf / p.ord_G;                     // whole groups; the rest of a frame forms a last, shorter group
-        const long g = tile / per_group;
-        int gl = p.ord_G;
-        long r = tile - g * per_group, gbase = g * p.ord_G;
-        if (g >= full) { gl = p.ord_Lf - full * p.ord_G; r = tile - (long)full * per_group; gbase = (long)full * p.ord_G; }
-        const int t = (int)(r / gl), j = (int)(r - (long)t * gl);
-        tile = (long)t * p.ord_Lf + gbase + j;
-    }
+    if (p.ord_T > 0) tile = conv_tile_at(p.ord_T, p.ord_Lf, p.ord_G, tile);
     const long p0 = (long)p.t_begin * HoWo + tile * X3_PIX;
     const int co0 = cob * NB * 32;
     const int nchunk = p.Cin >> 5;
@@ -899,6 +904,8 @@ __global__ __launch_bounds__(512, 2) void conv_dma2h_kernel(ConvP p) {
 // the phase instead of at its start (-0.7 %); the pieces fetched into registers one phase ahead and written with ds_write_b128 (a whole phase more for them to
 // arrive: +12 %, slower — two instructions per piece); every piece reading 1 KiB of contiguous memory, as a chunk-major plane layout would give (-8 % at most,
 // wrong results: not built).  What the step waits for is therefore neither the bytes, nor the issue of the requests, nor their latency alone.
+// Each tile reads through descriptors of its own, based at its own first input frame (conv_dma2h_kernel's addressing): the two tiles of a pair can be a
+// whole clip apart (ord_T x ord_G odd: 80 frames = 6.3 GB at 81 x 480 x 848 x 96), beyond one descriptor's 32-bit offsets.
 // =================================================================================================
 #define D2P_W_STAGE (6 * X3_W_PLANE)             // 36 KiB: three x-taps x two planes x [96][64 B]
 #define D2P_LDS (2 * D2P_W_STAGE + 2 * 2 * D2_A_PLANE)
@@ -922,27 +929,18 @@ __global__ __launch_bounds__(512, 2) void conv_dma2h_pair_kernel(ConvP p) {
     const int nk = nrow * nchunk;
     const unsigned OOB = 0xFFF00000u;
 
+    // Each tile has its own activation descriptors, based at its own first input frame: in the frame-interleaved order the two tiles of a
+    // pair can lie a whole clip apart (the last frame of one tile group and the first of the next when ord_T x ord_G is odd), farther than
+    // the 32-bit offsets of one descriptor reach (svi_vae_conv_plan reports the distance).
     long p0[2];
-    int t_base = 0x7fffffff;
+    int t_base[2];
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
         long tile = 2 * pair + s;                    // (a pair's second tile may lie past the last one: every pixel of it is masked out, nothing is stored)
-        if (p.ord_T > 0) {
-            const long per_group = (long)p.ord_T * p.ord_G;
-            const long n_tiles = (long)p.ord_T * p.ord_Lf;
-            if (tile < n_tiles) {
-                const int full = p.ord_Lf / p.ord_G;
-                const long g = tile / per_group;
-                int gl = p.ord_G;
-                long r = tile - g * per_group, gbase = g * p.ord_G;
-                if (g >= full) { gl = p.ord_Lf - full * p.ord_G; r = tile - (long)full * per_group; gbase = (long)full * p.ord_G; }
-                const int t = (int)(r / gl), j = (int)(r - (long)t * gl);
-                tile = (long)t * p.ord_Lf + gbase + j;
-            }
-        }
+        if (tile < (long)p.ord_T * p.ord_Lf) tile = conv_tile_at(p.ord_T, p.ord_Lf, p.ord_G, tile);
         p0[s] = (long)p.t_begin * HoWo + tile * X3_PIX;
         const int t_first = (int)(max(min(p0[s] - 1, P_total - 1), 0L) / HoWo);
-        t_base = min(t_base, max(t_first * p.st - p.pt, 0));
+        t_base[s] = max(t_first * p.st - p.pt, 0);
     }
     // ---- per-slot DMA bookkeeping
     unsigned a_off[2][A_SLOTS], a_mask[2][A_SLOTS], w_off[W_SLOTS];
@@ -971,7 +969,7 @@ __global__ __launch_bounds__(512, 2) void conv_dma2h_pair_kernel(ConvP p) {
                 }
                 a_mask[s][i] = m;
                 const int chunk = (lane & 3) ^ ((row >> 2) & 3);
-                a_off[s][i] = (unsigned)((((bt - t_base) * p.Hi + by) * p.Wi + ax) * p.ld_in) * 2u + (unsigned)chunk * 16u;
+                a_off[s][i] = (unsigned)((((bt - t_base[s]) * p.Hi + by) * p.Wi + ax) * p.ld_in) * 2u + (unsigned)chunk * 16u;
             }
         }
 #pragma unroll
@@ -984,11 +982,15 @@ __global__ __launch_bounds__(512, 2) void conv_dma2h_pair_kernel(ConvP p) {
             if (co0 + row < p.Cout) w_off[i] = (unsigned)((pl * p.plane_w3 + ((long)tc * p.Cout + co0 + row) * p.ld_w3 + chunk * 8) * 2);
         }
     }
-    const long base_el = (long)t_base * p.Hi * p.Wi * p.ld_in;
-    const long rem_bytes = ((long)p.Ti * p.Hi * p.Wi * p.ld_in - base_el) * 2;
-    const int win = (int)(unsigned)min(rem_bytes, 0xFFE00000L);
-    const __amdgpu_buffer_rsrc_t rs_h = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(p.in_h + base_el), 0, win, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_l = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(p.in_l + base_el), 0, win, 0x00020000);
+    __amdgpu_buffer_rsrc_t rs_h[2], rs_l[2];
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        const long base_el = (long)t_base[s] * p.Hi * p.Wi * p.ld_in;
+        const long rem_bytes = ((long)p.Ti * p.Hi * p.Wi * p.ld_in - base_el) * 2;
+        const int win = (int)(unsigned)min(rem_bytes, 0xFFE00000L);
+        rs_h[s] = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(p.in_h + base_el), 0, win, 0x00020000);
+        rs_l[s] = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(p.in_l + base_el), 0, win, 0x00020000);
+    }
     const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.w2h), 0, (int)(unsigned)min((long)2 * p.plane_w3 * 2, 0xFFE00000L), 0x00020000);
     bool left_ok[2], right_ok[2];
 #pragma unroll
@@ -1016,8 +1018,8 @@ __global__ __launch_bounds__(512, 2) void conv_dma2h_pair_kernel(ConvP p) {
             if (q < 34) {
                 const int pl = q / 17, r16 = q % 17;
                 const unsigned off = ((a_mask[S][i] >> rt) & 1u) ? a_off[S][i] + d_act : OOB;
-                if (pl == 0) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_h, (lptr_t)(As + r16 * 1024), 16, off, 0, 0, 0);
-                else __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_l, (lptr_t)(As + D2_A_PLANE + r16 * 1024), 16, off, 0, 0, 0);
+                if (pl == 0) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_h[S], (lptr_t)(As + r16 * 1024), 16, off, 0, 0, 0);
+                else __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_l[S], (lptr_t)(As + D2_A_PLANE + r16 * 1024), 16, off, 0, 0, 0);
             }
         }
     };
@@ -1148,42 +1150,58 @@ bool conv_planes_ok(const ConvP& p) {
            (long)(p.kt + 3) * p.Hi * p.Wi * p.ld_in * 2 < 0xFFE00000L && (long)2 * p.plane_w3 * 2 < 0xFFE00000L;
 }
 
+// What launch_conv_planes runs for a layer conv_planes_ok accepts, without device work (svi_vae_conv_plan reports it): the kernel and the tile order.
+struct ConvPlanesPlan {
+    int kernel;                      // 1 = conv_dma2h_kernel<1> (narrow head), 3 = conv_dma2h_kernel<3>, 2 = conv_dma2h_pair_kernel
+    int ord_T, ord_Lf, ord_G;        // ConvP's tile order (conv_tile_at; ord_T = 0: pixel order)
+    long tiles, workgroups;
+};
+ConvPlanesPlan conv_planes_plan(const ConvP& p) {
+    ConvPlanesPlan r{};
+    const long hw = (long)p.Ho * p.Wo;
+    const int frames = p.To - p.t_begin;
+    r.tiles = (frames * hw + X3_PIX - 1) / X3_PIX;
+    // frame-interleaved tile order (see the kernel) when frames are whole numbers of tiles and there is more than one
+    if (svi_switches().vae_tile_order && p.kt > 1 && frames > 1 && hw % X3_PIX == 0) {
+        r.ord_T = frames; r.ord_Lf = (int)(hw / X3_PIX);
+        r.ord_G = (int)std::max<long>(1, std::min<long>(r.ord_Lf, (16L * p.Wo + X3_PIX - 1) / X3_PIX));
+    }
+    const long ncob = (p.Cout + X3_CO - 1) / X3_CO;
+    if (p.Cout <= 32) {                  // narrow head
+        r.kernel = 1; r.workgroups = r.tiles;
+    } else if (svi_switches().vae_pair) {    // two tiles per workgroup sharing every step's weights
+        r.kernel = 2; r.workgroups = (r.tiles + 1) / 2 * ncob;
+    } else {
+        r.kernel = 3; r.workgroups = r.tiles * ncob;
+    }
+    return r;
+}
+
 svi_status launch_conv_planes(const ConvP& p, hipStream_t st) {
     SVI_REQUIRE(conv_planes_ok(p) && p.in_h && p.in_l, "conv: this layer cannot take fp16 input planes");
     SVI_REQUIRE(p.ld_out % 4 == 0 && (!p.res || p.ld_res % 4 == 0) && (((uintptr_t)p.res | (uintptr_t)p.out) & 15) == 0, "conv: output / residual alignment");
     const long pixels = (long)(p.To - p.t_begin) * p.Ho * p.Wo;
     if (pixels <= 0) return SVI_OK;
+    const ConvPlanesPlan pl = conv_planes_plan(p);
     ConvP q = p;
-    {   // frame-interleaved tile order (see the kernel) when frames are whole numbers of tiles and there is more than one
-        const long hw = (long)p.Ho * p.Wo;
-        const int frames = p.To - p.t_begin;
-        q.ord_T = 0;
-        if (svi_switches().vae_tile_order && p.kt > 1 && frames > 1 && hw % X3_PIX == 0) {
-            q.ord_T = frames; q.ord_Lf = (int)(hw / X3_PIX);
-            q.ord_G = (int)std::max<long>(1, std::min<long>(q.ord_Lf, (16L * p.Wo + X3_PIX - 1) / X3_PIX));
-        }
-    }
-    if (p.Cout <= 32) {                  // narrow head
+    q.ord_T = pl.ord_T;
+    if (pl.ord_T) { q.ord_Lf = pl.ord_Lf; q.ord_G = pl.ord_G; }
+    SVI_REQUIRE(pl.workgroups < (1L << 31), "conv: too many workgroups");
+    dim3 grid((unsigned)pl.workgroups, 1), block(512);
+    if (pl.kernel == 1) {
         SVI_REQUIRE((p.Cout + 3) / 4 * 4 <= p.ld_out && (!p.res || (p.Cout + 3) / 4 * 4 <= p.ld_res), "conv: a narrow head writes whole groups of four channels (Cout=%d, ld_out=%d)", p.Cout, p.ld_out);
         SVI_REQUIRE(p.Cout % 4 != 0 || (((uintptr_t)p.bias | (uintptr_t)p.w2_inv) & 15) == 0, "conv: bias / scale alignment");
-        dim3 grid((unsigned)((pixels + X3_PIX - 1) / X3_PIX), 1), block(512);
         SVI_TRY(svi_ensure_lds(reinterpret_cast<const void*>(conv_dma2h_kernel<1>), 2 * D2_STAGE));
         hipLaunchKernelGGL(conv_dma2h_kernel<1>, grid, block, 2 * D2_STAGE, st, q);
     } else {
         SVI_REQUIRE((((uintptr_t)p.bias) & 15) == 0, "conv: bias alignment");
-        const long nwg = ((pixels + X3_PIX - 1) / X3_PIX) * ((p.Cout + X3_CO - 1) / X3_CO);
-        SVI_REQUIRE(nwg < (1L << 31), "conv: too many workgroups");
-        dim3 grid((unsigned)nwg, 1), block(512);
-        if (svi_switches().vae_pair) {       // two tiles per workgroup sharing every step's weights (conv_dma2h_pair_kernel)
-            const long ntile = (pixels + X3_PIX - 1) / X3_PIX;
-            dim3 gridp((unsigned)(((ntile + 1) / 2) * ((p.Cout + X3_CO - 1) / X3_CO)), 1);
+        if (pl.kernel == 2) {
             SVI_TRY(svi_ensure_lds(reinterpret_cast<const void*>(conv_dma2h_pair_kernel), D2P_LDS));
-            hipLaunchKernelGGL(conv_dma2h_pair_kernel, gridp, block, D2P_LDS, st, q);
-            SVI_LAUNCH_CHECK();
-            return SVI_OK;
+            hipLaunchKernelGGL(conv_dma2h_pair_kernel, grid, block, D2P_LDS, st, q);
+        } else {
+            SVI_TRY(svi_ensure_lds(reinterpret_cast<const void*>(conv_dma2h_kernel<3>), 2 * D2_STAGE));
+            hipLaunchKernelGGL(conv_dma2h_kernel<3>, grid, block, 2 * D2_STAGE, st, q);
         }
-        SVI_TRY(svi_ensure_lds(reinterpret_cast<const void*>(conv_dma2h_kernel<3>), 2 * D2_STAGE));
-        hipLaunchKernelGGL(conv_dma2h_kernel<3>, grid, block, 2 * D2_STAGE, st, q);
     }
     SVI_LAUNCH_CHECK();
     return SVI_OK;
@@ -1253,6 +1271,51 @@ svi_status launch_conv_up_phases(ConvP p, const bf16* w3_up, hipStream_t st) {
 }
 
 }  // namespace
+
+// The plane-fed launch of a residual-block-shaped convolution (3x3x3 over Cin -> Cout, stride 1, causal, 'same'; input planes [frames][Ho][Wo][Cin]) under
+// the current switches, and what its activation descriptors must reach.  out8 = {kernel (0: the layer does not take fp16 planes, else
+// ConvPlanesPlan::kernel), ord_T, ord_Lf, ord_G, workgroups, the largest frame distance between the two tiles of one workgroup (0: one tile per workgroup),
+// the bytes the largest activation descriptor must address (whole input frames from its base to the last frame a tile behind it reads; the kernels' window
+// is 0xFFE00000), conv_planes_ok's own bound on that ((kt + 3) frames)}.  Host arithmetic only; the last two walk every workgroup of the launch.
+svi_status svi_vae_conv_choose(int Cin, int Cout, int kt, int frames, int Ho, int Wo, int64_t* out8) {
+    SVI_REQUIRE(out8 && Cin > 0 && Cout > 0 && kt > 0 && frames > 0 && Ho > 0 && Wo > 0, "svi_vae_conv_plan: bad argument");
+    for (int i = 0; i < 8; ++i) out8[i] = 0;
+    alignas(16) static const float dummy[4] = {0.f, 0.f, 0.f, 0.f};           // stands for the bound weight planes (conv_planes_ok asks they exist and are aligned)
+    ConvP p{};
+    p.Ti = p.To = frames; p.Hi = p.Ho = Ho; p.Wi = p.Wo = Wo; p.Cin = p.ld_in = Cin; p.Cout = Cout;
+    p.kt = kt; p.kh = p.kw = 3; p.st = p.sh = p.sw = 1; p.pt = kt - 1; p.ph = p.pw = 1;
+    p.ld_w3 = (Cin + 31) / 32 * 32; p.plane_w3 = (long)kt * 9 * Cout * p.ld_w3;
+    p.w2h = dummy; p.w2_inv = dummy; p.in_scale = 1.f;
+    if (!conv_planes_ok(p)) return SVI_OK;
+    const ConvPlanesPlan pl = conv_planes_plan(p);
+    const long HoWo = (long)Ho * Wo, P_total = (long)frames * HoWo, frame_bytes = HoWo * Cin * 2;
+    const int per_wg = pl.kernel == 2 ? 2 : 1;
+    long span = 0, desc_frames = 0;
+    for (long w = 0; w * per_wg < pl.tiles; ++w) {
+        int t0 = -1;
+        for (int s = 0; s < per_wg && w * per_wg + s < pl.tiles; ++s) {       // (a pair's second tile past the last one reads nothing)
+            const long p0 = conv_tile_at(pl.ord_T, pl.ord_Lf, pl.ord_G, w * per_wg + s) * X3_PIX;
+            // as the kernels: the descriptor of the tile at p0 is based at the first frame its strip [p0 - 1, p0 - 1 + D2_ROWS) reads
+            const int t_first = (int)(std::max(std::min(p0 - 1, P_total - 1), 0L) / HoWo);
+            const int t_last = (int)(std::min(p0 - 2 + D2_ROWS, P_total - 1) / HoWo);
+            const int base = std::max(t_first * p.st - p.pt, 0), top = std::min(t_last * p.st - p.pt + kt - 1, p.Ti - 1);
+            desc_frames = std::max<long>(desc_frames, top - base + 1);
+            const int t = (int)(p0 / HoWo);
+            if (t0 >= 0) span = std::max<long>(span, t > t0 ? t - t0 : t0 - t);
+            t0 = t;
+        }
+    }
+    out8[0] = pl.kernel; out8[1] = pl.ord_T; out8[2] = pl.ord_Lf; out8[3] = pl.ord_G; out8[4] = pl.workgroups;
+    out8[5] = span; out8[6] = desc_frames * frame_bytes; out8[7] = (long)(kt + 3) * frame_bytes;
+    return SVI_OK;
+}
+
+// conv_tile_at over every launch position: out[i] = the pixel tile workgroup position i computes
+svi_status svi_vae_tile_order_fill(int ord_T, int ord_Lf, int ord_G, int64_t* out) {
+    SVI_REQUIRE(out && ord_T > 0 && ord_Lf > 0 && ord_G > 0 && ord_G <= ord_Lf, "svi_vae_tile_order: bad argument");
+    for (long i = 0; i < (long)ord_T * ord_Lf; ++i) out[i] = conv_tile_at(ord_T, ord_Lf, ord_G, i);
+    return SVI_OK;
+}
 
 // fp32 linear layer C = A W^T + bias (+ res) on the exact-fp32 MFMA kernel (a 1x1x1 "convolution": pixels = rows).  Used by the CLIP
 // image encoder, which the reference runs in fp32 (pipelines/svi_video.py:307-309).

@@ -86,6 +86,8 @@ SYMBOLS = [
     ("svi_fp8_e4m3_to_bf16", _i32, [_vp, _vp, _i64, _vp]),
     ("svi_gemm_plan", _i32, [_i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(_i32)]),
     ("svi_attention_plan", _i32, [_i32, _i32, _i32, _i32, C.POINTER(_i32)]),
+    ("svi_vae_conv_plan", _i32, [_i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(_i64)]),
+    ("svi_vae_tile_order", _i32, [_i32, _i32, _i32, C.POINTER(_i64)]),
     ("svi_prof_enable", _i32, [_i32]),
     ("svi_prof_summary", _i32, [C.c_char_p, _i64]),
     ("svi_prof_select", _i32, [C.c_char_p]),
@@ -200,6 +202,26 @@ def attention_plan(s_q: int, s_kv: int, heads: int, compute_units: int = 256) ->
     out = (_i32 * 4)()
     check(lib().svi_attention_plan(s_q, s_kv, heads, compute_units, out), "svi_attention_plan")
     return {"kernel": out[0], "whole": out[1], "pieces": out[2], "workgroups": out[3]}
+
+
+VAE_CONV_KERNELS = {0: None, 1: "dma2h<1>", 3: "dma2h<3>", 2: "pair"}
+
+
+def vae_conv_plan(Cin: int, Cout: int, kt: int, frames: int, Ho: int, Wo: int) -> dict:
+    """The plane-fed launch of a VAE residual-block convolution (3x3x3, stride 1, causal) under the current switches (see include/svi_hip.h):
+    kernel None = the layer does not take fp16 planes; pair_span = frames between the two tiles of one workgroup; desc_bytes = what the largest
+    activation descriptor must address, guard_bytes = the launch guard's bound on it."""
+    out = (_i64 * 8)()
+    check(lib().svi_vae_conv_plan(Cin, Cout, kt, frames, Ho, Wo, out), "svi_vae_conv_plan")
+    return {"kernel": VAE_CONV_KERNELS[out[0]], "ord_T": out[1], "ord_Lf": out[2], "ord_G": out[3], "workgroups": out[4], "pair_span": out[5],
+            "desc_bytes": out[6], "guard_bytes": out[7]}
+
+
+def vae_tile_order(ord_T: int, ord_Lf: int, ord_G: int) -> list:
+    """Pixel tile (frame-major) of each launch position under the frame-interleaved order."""
+    out = (_i64 * (ord_T * ord_Lf))()
+    check(lib().svi_vae_tile_order(ord_T, ord_Lf, ord_G, out), "svi_vae_tile_order")
+    return list(out)
 
 
 def prof_select(tags=None) -> None:

@@ -43,7 +43,7 @@ def kernel_table(tmp_path):
 
 def test_hot_kernels_run_without_scratch_and_fit_their_occupancy(tmp_path):
     """(a) every kernel a default C2 step or the VAE decode launches runs without scratch memory and without spilled registers; (b) the occupancy each
-    one is written for holds: two waves per SIMD (<= 256 VGPRs) for the tiled GEMM and the resident cross-attention, ONE wave per SIMD owning the
+    one is written for holds: two waves per SIMD (<= 256 VGPRs) for the tiled GEMM, the resident cross-attention and the VAE's plane-fed convolutions, ONE wave per SIMD owning the
     whole 512-entry file for the self-attention kernel's optimistic pass (the pass that is 64 % of a step).  The rarely taken passes of the
     self-attention kernel (single-pass with rescaling, the flagged second pass) are allowed their 8 spilled registers — they are listed, not hidden."""
     t = kernel_table(tmp_path)
@@ -55,7 +55,7 @@ def test_hot_kernels_run_without_scratch_and_fit_their_occupancy(tmp_path):
         return got
     clean = {}
     for prefix in ("flash_cross_resident_kernel<", "gemm_bf16_nt_256e_kernel<", "gemm_bf16_nt_kernel", "gemm_mx8_nt_256_kernel", "ln_mod_rows_kernel<", "rmsnorm_rope_rows_kernel<",
-                   "row_rs_kernel", "cfg_step_kernel", "conv_dma2h_kernel<", "flash_fwd_kernel<"):
+                   "row_rs_kernel", "cfg_step_kernel", "conv_dma2h_kernel<", "conv_dma2h_pair_kernel", "flash_fwd_kernel<"):
         clean.update(family(prefix))
     main_pass = {k: v for k, v in family("flash_fwd2_kernel<").items() if re.match(r"flash_fwd2_kernel<\d+, (true|false), 1, ", k)}
     assert len(main_pass) == 6, sorted(main_pass)
@@ -68,6 +68,9 @@ def test_hot_kernels_run_without_scratch_and_fit_their_occupancy(tmp_path):
     for k, v in family("flash_cross_resident_kernel<").items():
         assert v["vgpr_count"] <= 256 and v["group_segment_fixed_size"] == 0, (k, v)          # two waves per SIMD; LDS is dynamic (128 KiB + the mask table)
     for k, v in family("gemm_bf16_nt_256e_kernel<").items():
+        assert v["vgpr_count"] <= 256, (k, v)
+    # the VAE's plane-fed convolutions (the decode's default conv_dma2h_pair_kernel among them): __launch_bounds__(512, 2) = two waves per SIMD
+    for k, v in {**family("conv_dma2h_kernel<"), **family("conv_dma2h_pair_kernel")}.items():
         assert v["vgpr_count"] <= 256, (k, v)
     # round 6: the 128^2 tile's loops — <1, 256> shares a SIMD with a second workgroup, <4, 512> (the C1-size step's projections: at most one workgroup per CU)
     # brings its own second wave per SIMD, <4, 256> (A/B only) owns the file

@@ -278,3 +278,55 @@ def test_block_and_unstacked_pair_at_75600_tokens_720p(hip):
         assert torch.equal(a, m.forward(lat, ts, cp)) and torch.equal(b, m.forward(lat, ts, cn))
     finally:
         m.context_cache(False)
+
+
+def _vae_rel(a, b):
+    return float((a.double() - b.double()).norm() / b.double().norm())
+
+
+@pytest.mark.parametrize("lat_frames,h,w", [(21, 60, 106), (11, 160, 90)])
+def test_vae_pair_kernel_where_tile_groups_are_odd(hip, lat_frames, h, w):
+    """Decode and encode at sizes whose full-resolution convolutions have an odd T x G (tile groups x frames, svi_vae_conv_plan): 81 frames of 480 x 848
+    (G = 53) and 41 frames of portrait 720p, 1280 x 720 (G = 45).  There the two tiles of a pair workgroup can be the last frame of one tile group and the
+    first frame of the next — 80 frames = 6.3 GB (40 frames = 7.1 GB) apart.  The default two-tile kernel against the one-tile kernel (SVI_VAE_PAIR=0: the
+    same products in the same order, bit for bit) and against the on-the-fly split (SVI_VAE_DMA=0, another kernel family: rel-L2 <= 5e-6, max-abs <= 5e-5,
+    the bounds of test_gpu_vae.py's plane-fed comparison); finite outputs; the first 5 decoded frames equal the decode of the first 2 latent frames."""
+    import synth
+    from svi_hip import _lib as L
+    v = hip.WanVideoVAE.from_state_dict({k: torch.from_numpy(a) for k, a in synth.vae_state_dict(500).items()})
+    g = torch.Generator(device="cuda").manual_seed(40 + lat_frames)
+    z = torch.randn((16, lat_frames, h, w), generator=g, device="cuda")
+    frames = 4 * (lat_frames - 1) + 1
+    vid = torch.tanh(torch.randn((3, frames, 8 * h, 8 * w), generator=g, device="cuda"))
+    p = L.vae_conv_plan(96, 96, 3, frames, 8 * h, 8 * w)
+    assert p["kernel"] == "pair" and (p["ord_T"] * p["ord_G"]) % 2 == 1 and p["pair_span"] == frames - 1, p
+
+    def run():
+        return v.decode([z], device="cuda")[0], v.encode([vid], device="cuda")[0]
+    a_dec, a_enc = run()
+    assert tuple(a_dec.shape) == (3, frames, 8 * h, 8 * w) and tuple(a_enc.shape) == (16, lat_frames, h, w)
+    assert torch.isfinite(a_dec).all() and torch.isfinite(a_enc).all()
+    part = v.decode([z[:, :2].contiguous()], device="cuda")[0]
+    causal = float((a_dec[:, :5] - part).abs().max())
+    del part
+    L.set_switch("SVI_VAE_PAIR", 0)
+    try:
+        b_dec, b_enc = run()
+    finally:
+        L.set_switch("SVI_VAE_PAIR", None)
+    same_dec, same_enc = bool(torch.equal(a_dec, b_dec)), bool(torch.equal(a_enc, b_enc))
+    del b_dec, b_enc
+    L.set_switch("SVI_VAE_DMA", 0)
+    try:
+        c_dec, c_enc = run()
+    finally:
+        L.set_switch("SVI_VAE_DMA", None)
+    rd, md = _vae_rel(a_dec, c_dec), float((a_dec - c_dec).abs().max())
+    re, me = _vae_rel(a_enc, c_enc), float((a_enc - c_enc).abs().max())
+    from gpu_util import report
+    report("vae_pair_odd_tile_groups", size=[8 * h, 8 * w], frames=frames, pair_bits_decode=same_dec, pair_bits_encode=same_enc,
+           dma_decode_rel=rd, dma_decode_maxabs=md, dma_encode_rel=re, dma_encode_maxabs=me, causality_maxabs=causal)
+    assert torch.isfinite(c_dec).all() and torch.isfinite(c_enc).all()
+    assert same_dec and same_enc, (same_dec, same_enc)
+    assert rd < 5e-6 and md < 5e-5 and re < 5e-6 and me < 5e-5, (rd, md, re, me)
+    assert causal < 1e-5, causal

@@ -203,12 +203,14 @@ def test_plane_fed_convolutions_agree_with_the_on_the_fly_split(vae, shape):
     assert rd < 5e-6 and md < 5e-5 and re < 5e-6 and me < 5e-5, (rd, md, re, me)
 
 
-@pytest.mark.parametrize("shape", [(16, 3, 12, 20), (16, 2, 30, 52), (16, 2, 5, 3), (16, 1, 7, 9), (16, 4, 30, 52)])
+@pytest.mark.parametrize("shape", [(16, 3, 12, 20), (16, 2, 30, 52), (16, 2, 5, 3), (16, 1, 7, 9), (16, 4, 30, 52), (16, 3, 8, 6), (16, 2, 4, 5)])
 def test_two_tiles_per_workgroup_give_the_one_tile_kernels_bits(vae, shape):
     """conv_dma2h_pair_kernel (round 6, the default: two 256-pixel tiles per workgroup share every K step's weights) against conv_dma2h_kernel<3>
     (SVI_VAE_PAIR=0): the same products in the same order per pixel — decode and encode bit for bit, on grids with an odd number of tiles (the pair's second
     tile lies past the end), tiles that straddle image rows and frames, one frame, and the frame-interleaved tile order (whole tiles per frame: 30 x 52 latent
-    = 240 x 416 px = 390 tiles per frame)."""
+    = 240 x 416 px = 390 tiles per frame).  8 x 6 latent: 64 x 48 px = 12 tiles per frame in groups of 3 over 9 frames — 27 tiles per group, so pairs join
+    the last frame of one group to the first frame of the next (svi_vae_conv_plan's pair span: 8 frames); at 32 x 24 px 3 tiles per frame in groups of 2
+    (a last group of one).  4 x 5 latent: 32 x 40 px = 5 tiles per frame in groups of 3 (a shorter last group), 5 frames."""
     from svi_hip import _lib as L
     v, _ = vae
     z = torch.from_numpy(synth.randn(621, *shape)).cuda()
@@ -242,3 +244,22 @@ def test_upsample_convolution_phases_agree_with_the_nine_tap_form(vae, shape):
     r, mx, _ = errs(a, b)
     report("vae_upsample_phases_vs_nine_taps", shape=list(shape), decode_rel=r, decode_maxabs=mx)
     assert r < 5e-6 and mx < 5e-5, (r, mx)
+
+
+def test_pair_tile_order_shape_vs_oracle(vae):
+    """The default decode and encode at the latent 8 x 6 of the pair test above (64 x 48 px, 9 frames: tile groups whose pairs span the clip) against
+    the oracle, within the file's bounds."""
+    v, sd = vae
+    with torch.no_grad():
+        z = torch.from_numpy(synth.randn(631, 1, 16, 3, 8, 6))
+        want = wvo.vae_decode(sd, z)[0]
+        got = v.decode([z[0].cuda()], device="cuda")[0]
+        r, mx, _ = errs(got, want)
+        vid = torch.from_numpy(np.tanh(synth.randn(632, 1, 3, 9, 64, 48)))
+        want_e = wvo.vae_encode(sd, vid)[0]
+        got_e = v.encode([vid[0].cuda()], device="cuda")[0]
+        re, me, _ = errs(got_e, want_e)
+    report("vae_pair_order_oracle", decode_rel=r, decode_maxabs=mx, encode_rel=re, encode_maxabs=me)
+    assert got.shape == want.shape and got_e.shape == want_e.shape
+    assert r < 2e-5 and mx < 2e-4, (r, mx)
+    assert re < 2e-5 and me < 2e-4, (re, me)

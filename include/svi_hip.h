@@ -46,7 +46,7 @@ typedef enum {
     SVI_ERR_OOM = 5
 } svi_status;
 
-typedef enum { SVI_BF16 = 0, SVI_F32 = 1 } svi_dtype;
+typedef enum { SVI_BF16 = 0, SVI_F32 = 1, SVI_F16 = 2 /* LoRA operands only (svi_lora_merge_e4m3) */ } svi_dtype;
 
 typedef void* svi_stream;
 typedef struct svi_dit svi_dit;
@@ -351,6 +351,22 @@ svi_status svi_cfg3_step(void* latents, const void* cond, const void* uncond, co
  * casts them to bf16 in front of every use (vram_management/layers.py:65-71, cast_to).  The cast is exact, so it is done once:
  * out bf16 [n] = bf16(in e4m3fn [n]); bind the result with svi_dit_bind_weight.  (svi_hip.WanDiT.bind does this for fp8 tensors.) */
 svi_status svi_fp8_e4m3_to_bf16(const void* in, void* out, int64_t n, svi_stream stream);
+
+/* The cast back: out e4m3fn [n] = cast(in [n]), in fp32 (SVI_F32) or bf16 (SVI_BF16, widened exactly), with the semantics of torch's
+ * `tensor.to(torch.float8_e4m3fn)`: round to nearest even, subnormals down to 2^-9 (2^-10 ties to 0), NO saturation — 464 still rounds
+ * to 448, anything above it and +-inf become NaN, NaN stays NaN.  What `load_models(torch_dtype=torch.float8_e4m3fn)` does to every
+ * parameter (svi_hip.checkpoint.load_dit(torch_dtype=...)), and the last step of svi_lora_merge_e4m3. */
+svi_status svi_f32_to_fp8_e4m3(const void* in, svi_dtype in_dtype, void* out, int64_t n, svi_stream stream);
+
+/* LoRA merge into an FP8-stored weight, in place (GeneralLoRAFromPeft.load when the model's parameters are float8_e4m3fn,
+ * models/lora.py:231-264: the computation dtype becomes fp32):
+ *     w8 <- e4m3fn( fp32(w8) + alpha * mm( fp32(up), fp32(down) ) )
+ * with the reference's three fp32 rounding points (product, scaling, sum) and the cast above.  w8 e4m3fn codes [out_f, in_f], contiguous,
+ * 8-byte aligned; up [out_f, r]; down_t [in_f, r] = down TRANSPOSED (both operands k-contiguous, as svi_gemm_bf16 takes the bf16 merge's);
+ * both operands of `dtype` (SVI_BF16, SVI_F16 or SVI_F32 — kept in that precision: bf16 on the bf16 matrix instruction, the other two
+ * widened to fp32 on the fp32 one), contiguous and 16-byte aligned.  in_f % 8 == 0 and r % 8 == 0; any out_f. */
+svi_status svi_lora_merge_e4m3(void* w8, int32_t out_f, int32_t in_f, const void* up, const void* down_t, svi_dtype dtype, int32_t r, float alpha,
+                               svi_stream stream);
 
 /* ------------------------------------------------------------------ measurement ----------- */
 /* Per-kernel timing with HIP events recorded on the launch stream (so it measures the kernels where

@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SVI_HIP_LIB") or os.path.join(_HERE, "libsvi_hip.so")   # SVI_HIP_LIB: A/B a variant build (tools/build_variant.py)
 
 SVI_OK = 0
-SVI_BF16, SVI_F32 = 0, 1
+SVI_BF16, SVI_F32, SVI_F16 = 0, 1, 2
 EPI_BIAS, EPI_BIAS_GELU_TANH, EPI_BIAS_GATE_RES, EPI_BIAS_GELU_ERF, EPI_BIAS_SILU, EPI_BIAS_RELU = 0, 1, 2, 3, 4, 5
 
 # every symbol include/svi_hip.h declares: (name, restype, argtypes)
@@ -84,6 +84,8 @@ SYMBOLS = [
     ("svi_gemm_mx8_wscaled", _i32, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp]),
     ("svi_dit_proj_mx8", _i32, [_vp, _i32]),
     ("svi_fp8_e4m3_to_bf16", _i32, [_vp, _vp, _i64, _vp]),
+    ("svi_f32_to_fp8_e4m3", _i32, [_vp, _i32, _vp, _i64, _vp]),
+    ("svi_lora_merge_e4m3", _i32, [_vp, _i32, _i32, _vp, _vp, _i32, _i32, _f32, _vp]),
     ("svi_gemm_plan", _i32, [_i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(_i32)]),
     ("svi_attention_plan", _i32, [_i32, _i32, _i32, _i32, C.POINTER(_i32)]),
     ("svi_vae_conv_plan", _i32, [_i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(_i64)]),

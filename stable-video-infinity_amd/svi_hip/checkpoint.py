@@ -9,6 +9,7 @@ checkpoint needs no table entry.  Tokenisers stay with the reference.
 """
 from __future__ import annotations
 
+import contextlib
 from typing import Dict, Sequence, Union
 
 import torch
@@ -46,11 +47,39 @@ def infer_dit_config(shapes: Dict[str, Sequence[int]], patch_size=(1, 2, 2), eps
     return cfg
 
 
-def load_dit(paths: Union[str, Sequence[str]], cfg: dict = None, device="cuda"):
+_dit_storage = None          # what load_dit's torch_dtype=None stands for (dit_storage)
+
+
+@contextlib.contextmanager
+def dit_storage(torch_dtype):
+    """Inside the block, load_dit calls that do not name a torch_dtype store the DiT as `torch_dtype` (torch.float8_e4m3fn, or None = as stored):
+    a caller that cannot pass the argument down — a script whose loading code is someone else's — selects the FP8 storage mode from outside."""
+    global _dit_storage
+    if torch_dtype not in (None, torch.float8_e4m3fn):
+        raise ValueError(f"dit_storage: torch_dtype must be None or torch.float8_e4m3fn, got {torch_dtype}")
+    before, _dit_storage = _dit_storage, torch_dtype
+    try:
+        yield
+    finally:
+        _dit_storage = before
+
+
+def load_dit(paths: Union[str, Sequence[str]], cfg: dict = None, device="cuda", torch_dtype=None):
     """A WanDiT bound to the tensors of a (sharded) safetensors checkpoint.  bf16 and float8_e4m3fn tensors are bound as stored (fp8
-    through the exact bind-time cast); anything else is cast to bf16, the dtype the pipelines run the DiT in.  cfg=None: read off the shapes."""
+    through the exact bind-time cast); anything else is cast to bf16, the dtype the pipelines run the DiT in.  cfg=None: read off the shapes.
+    torch_dtype=torch.float8_e4m3fn: the reference's FP8 storage mode from stock shards (load_models(torch_dtype=...), test_svi.py:337) —
+    every parameter is stored as e4m3, cast on the device with torch's rounding (ops.f32_to_fp8_e4m3); None: as stored, unless the call runs inside a
+    dit_storage(...) block."""
     from .dit import WanDiT
+    if torch_dtype is None:
+        torch_dtype = _dit_storage
+    if torch_dtype not in (None, torch.float8_e4m3fn):
+        raise ValueError(f"load_dit: torch_dtype must be None or torch.float8_e4m3fn, got {torch_dtype}")
     sd = load_safetensors(paths, device=device)
+    if torch_dtype is not None:
+        from .ops import f32_to_fp8_e4m3
+        sd = {k: v if v.dtype == torch.float8_e4m3fn else f32_to_fp8_e4m3(v if v.dtype in (torch.float32, torch.bfloat16) else v.float())
+              for k, v in sd.items()}
     sd = {k: (v if v.dtype in (torch.bfloat16, torch.float8_e4m3fn) else v.to(torch.bfloat16)).contiguous() for k, v in sd.items()}
     if cfg is None:
         cfg = infer_dit_config(sd)

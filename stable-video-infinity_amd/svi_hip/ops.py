@@ -132,6 +132,19 @@ def fp8_e4m3_to_bf16(t: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def f32_to_fp8_e4m3(t: torch.Tensor) -> torch.Tensor:
+    """float8_e4m3fn copy of an fp32 or bf16 tensor with the semantics of torch's own `t.to(torch.float8_e4m3fn)` (round to nearest even,
+    subnormals to 2^-9, no saturation: above 464 -> NaN), on the device: what the reference's `load_models(torch_dtype=torch.float8_e4m3fn)`
+    does to every parameter, and the cast a LoRA merge into fp8-stored weights ends in (svi_lora_merge_e4m3)."""
+    if t.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"expected an fp32 or bf16 tensor, got {t.dtype}")
+    src = t.to(device="cuda").contiguous()
+    out = torch.empty(src.shape, dtype=torch.float8_e4m3fn, device=src.device)
+    L.check(L.lib().svi_f32_to_fp8_e4m3(L.ptr(src), L.SVI_F32 if src.dtype == torch.float32 else L.SVI_BF16, L.ptr(out), src.numel(),
+                                        L.current_stream()), "f32_to_fp8_e4m3")
+    return out
+
+
 def cfg3_step_(latents: torch.Tensor, cond: torch.Tensor, uncond: torch.Tensor, drop_text: torch.Tensor, text_scale: float, audio_scale: float,
                dsigma: float) -> torch.Tensor:
     """latents += (uncond + text_scale*(cond - drop_text) + audio_scale*(drop_text - uncond)) * dsigma, in place, bf16 op-by-op

@@ -33,8 +33,13 @@ from the shard's first row, so the deferred-rescale events of the softmax (taken
 results agree within the attention kernel's stated tolerance, bit for bit when Ls is a multiple of 256.
 
 Every arithmetic kernel is the one the single-GPU forward uses, on the same operands per row / per head, so the result is
-bit-identical to `WanDiT.forward` for any P and G (tests/test_gpu_sp.py runs P = 1, 2, 4 shards on one GPU with the exchange
-simulated in-process and with real process groups; tests/test_dist_gloo.py runs the layout algebra over gloo on CPU tensors).
+bit-identical to `WanDiT.forward` for any P and G.
+
+The block schedule of each mode is written ONCE (ulysses_blocks, gather_blocks; run_blocks adds the TeaCache modes) over the shards
+that live in this process and a transport: GroupTransport (one shard; collectives of a process group) or LocalTransport (P shards in
+one process; device copies).  forward_distributed[_pair] and forward_local[_pair] differ in that choice alone, so the in-process
+tests (tests/test_gpu_sp.py: P = 1, 2, 4 shards on one GPU) run the very loop a rank runs; tests/test_sp_schedule.py pins the order
+of stages, exchanges and waits on the CPU, tests/test_dist_gloo.py runs the layout algebra over gloo on CPU tensors.
 """
 from __future__ import annotations
 
@@ -117,24 +122,77 @@ def _staged(t: torch.Tensor, group) -> bool:
     return t.is_cuda and dist.get_backend(group) == "gloo"
 
 
+def _wait(work) -> None:
+    """Wait for an exchange where its data is needed; None: the exchange was synchronous."""
+    if work is not None:
+        work.wait()
+
+
+class GroupTransport:
+    """The exchanges of the ONE shard of this process with the other ranks of a process group.  RCCL: async collectives on the communicator's
+    stream (the caller enqueues more kernels and waits on the returned handle where the data is needed); a staged group: through the host,
+    synchronous, handle None."""
+
+    def __init__(self, group=None):
+        self.group = group
+
+    def all_to_all(self, recvs, sends):
+        """[P, ...] pieces: recv[i] = rank i's send[my rank]."""
+        (recv,), (send,) = recvs, sends
+        if _staged(send, self.group):
+            host = send.cpu().contiguous()
+            out = torch.empty_like(host)
+            dist.all_to_all_single(out, host, group=self.group)
+            recv.copy_(out)
+            return None
+        return dist.all_to_all_single(recv, send, group=self.group, async_op=True)
+
+    def all_gather(self, outs, mines):
+        """out [P, ...] <- every rank's `mine`."""
+        (out,), (mine,) = outs, mines
+        if _staged(mine, self.group):
+            host = mine.cpu().contiguous()
+            got = [torch.empty_like(host) for _ in range(out.shape[0])]
+            dist.all_gather(got, host, group=self.group)
+            out.copy_(torch.stack(got))
+            return None
+        return dist.all_gather_into_tensor(out, mine.contiguous(), group=self.group, async_op=True)
+
+    def gather_rows(self, rows) -> torch.Tensor:
+        """-> the head rows of all ranks, rank-major (once per forward, synchronous)."""
+        (rows,) = rows
+        src = rows.cpu() if _staged(rows, self.group) else rows
+        gathered = [torch.empty_like(src) for _ in range(dist.get_world_size(self.group))]
+        dist.all_gather(gathered, src.contiguous(), group=self.group)
+        return torch.cat(gathered, dim=0).to(rows.device)
+
+
+class LocalTransport:
+    """The same exchanges among the P shards living in one process: device copies between their buffers on the current stream, handle None."""
+
+    def all_to_all(self, recvs, sends):
+        for j, recv in enumerate(recvs):                 # shard j receives piece j of every shard i
+            for i, send in enumerate(sends):
+                recv[i].copy_(send[j])
+
+    def all_gather(self, outs, mines):
+        for out in outs:
+            for i, mine in enumerate(mines):
+                out[i].copy_(mine)
+
+    def gather_rows(self, rows) -> torch.Tensor:
+        return torch.cat(list(rows), dim=0)
+
+
 def all_to_all(send: torch.Tensor, group=None) -> torch.Tensor:
     """send [P, ...] -> recv [P, ...]: recv[i] = rank i's send[my rank]   (RCCL on GPUs, gloo in the tests)."""
-    if _staged(send, group):
-        host = send.cpu().contiguous()
-        out = torch.empty_like(host)
-        dist.all_to_all_single(out, host, group=group)
-        return out.to(send.device)
     recv = torch.empty_like(send)
-    dist.all_to_all_single(recv, send.contiguous(), group=group)
+    _wait(GroupTransport(group).all_to_all([recv], [send.contiguous()]))
     return recv
 
 
 def all_gather_rows(rows: torch.Tensor, group=None) -> torch.Tensor:
-    world = dist.get_world_size(group)
-    src = rows.cpu() if _staged(rows, group) else rows
-    gathered = [torch.empty_like(src) for _ in range(world)]
-    dist.all_gather(gathered, src.contiguous(), group=group)
-    return torch.cat(gathered, dim=0).to(rows.device)
+    return GroupTransport(group).gather_rows([rows])
 
 
 def all_to_all_local(sends: Sequence[torch.Tensor]) -> List[torch.Tensor]:
@@ -344,30 +402,6 @@ class SequenceShard:
 
 
 # ---- drivers -----------------------------------------------------------------------------------------------------------------
-def _exchange(recv: torch.Tensor, send: torch.Tensor, group, overlap: bool):
-    """all-to-all of [P, n] pieces.  RCCL: an async collective on the communicator's stream (the caller waits on the returned
-    handle where the data is needed, so the next kernels enqueue meanwhile); gloo (tests): staged through the host, synchronous."""
-    if _staged(send, group):
-        host = send.cpu().contiguous()
-        out = torch.empty_like(host)
-        dist.all_to_all_single(out, host, group=group)
-        recv.copy_(out)
-        return None
-    return dist.all_to_all_single(recv, send, group=group, async_op=overlap)
-
-
-def _all_gather_into(out: torch.Tensor, mine: torch.Tensor, group, overlap: bool = False):
-    """out [P, ...] <- every rank's `mine` (RCCL all-gather; gloo in the tests goes through the host).  overlap: an async collective on the
-    communicator's stream — the caller enqueues more kernels and waits on the returned handle where the data is needed."""
-    if _staged(mine, group):
-        host = mine.cpu().contiguous()
-        got = [torch.empty_like(host) for _ in range(out.shape[0])]
-        dist.all_gather(got, host, group=group)
-        out.copy_(torch.stack(got))
-        return None
-    return dist.all_gather_into_tensor(out, mine.contiguous(), group=group, async_op=overlap)
-
-
 def _armed(dits: Sequence[WanDiT], audio_embed_tuple):
     """Arm every handle with the talk variant's audio windows for one forward (None: leave whatever is armed); returns the disarm callback."""
     if audio_embed_tuple is None:
@@ -381,6 +415,91 @@ def _armed(dits: Sequence[WanDiT], audio_embed_tuple):
     return disarm
 
 
+def ulysses_blocks(shards, tr) -> None:
+    """The block loop of the Ulysses mode for the shards of this process (one branch or a stacked pair: the same exchanges, pieces nb x as long).
+    All q | k exchanges are issued up front; group g's attention waits for its own two only and its output leaves while group g + 1 attends."""
+    bufs, G = [sh.buf for sh in shards], shards[0].G
+    for layer in range(shards[0].dit.num_layers):
+        for sh in shards:
+            sh.block_qkv(layer)
+        wv = tr.all_to_all([b.vt_recv for b in bufs], [b.vt_send for b in bufs])
+        wq = [[tr.all_to_all([b.qk_recv[o, g] for b in bufs], [b.qk_send[o, g] for b in bufs]) for o in (0, 1)] for g in range(G)]
+        _wait(wv)
+        for sh in shards:
+            sh.unpack_v()
+        wo = []
+        for g in range(G):
+            for w in wq[g]:
+                _wait(w)
+            for sh in shards:
+                sh.attention(g)
+            wo.append(tr.all_to_all([b.o_recv[g] for b in bufs], [b.o_send[g] for b in bufs]))
+        for w in wo:
+            _wait(w)
+        for sh in shards:
+            sh.block_rest(layer)
+
+
+def gather_blocks(shards, tr) -> None:
+    """The block loop of the gather mode: V^T leaves first, so its all-gather runs under the q | k projection and RoPE."""
+    bufs = [sh.buf for sh in shards]
+    for layer in range(shards[0].dit.num_layers):
+        for sh in shards:
+            sh.block_v_rows(layer)
+        wv = tr.all_gather([b.vt_all for b in bufs], [b.vt for b in bufs])
+        for sh in shards:
+            sh.block_qk_rows(layer)
+        wk = tr.all_gather([b.k_all for b in bufs], [b.k for b in bufs])
+        _wait(wv)
+        _wait(wk)
+        for sh in shards:
+            sh.attention_rows()
+        for sh in shards:
+            sh.block_rest_rows(layer)
+
+
+def run_blocks(shards, tr, tea_mode: int = 0, residuals=None) -> None:
+    """All blocks of one forward on shards that have begun, in their mode's schedule.  tea_mode / residuals (TeaCache, one [Ls, dim] tensor per shard):
+    1 = also write every shard's residual rows; 2 = skip the blocks and add the residuals — no exchange at all."""
+    residuals = residuals if tea_mode else [None] * len(shards)
+    if tea_mode == 2:
+        for sh, res in zip(shards, residuals):
+            sh.tea(2, res)
+        return
+    if tea_mode == 1:
+        for sh in shards:
+            sh.tea(0)
+    (gather_blocks if shards[0].mode == "gather" else ulysses_blocks)(shards, tr)
+    if tea_mode == 1:
+        for sh, res in zip(shards, residuals):
+            sh.tea(1, res)
+
+
+def _forward(shards, tr, x, timestep, context, tea_mode, residuals, audio_embed_tuple, cond) -> torch.Tensor:
+    disarm = _armed([sh.dit for sh in shards], audio_embed_tuple)
+    try:
+        for sh in shards:
+            sh.begin(x, timestep, context, **cond)
+        run_blocks(shards, tr, tea_mode, residuals)
+        return shards[0].unpatchify(tr.gather_rows([sh.head() for sh in shards]))
+    finally:
+        disarm()
+
+
+def _pair_outputs(sh: SequenceShard, rows_all: torch.Tensor):
+    """rows_all [P, 2 Ls, ld] (every rank's stacked head rows, rank-major) -> (cond, uncond) latents."""
+    P, Ls = rows_all.shape[0], sh.Ls
+    return tuple(sh.unpatchify(rows_all[:, br * Ls:(br + 1) * Ls].reshape(P * Ls, -1)) for br in range(2))
+
+
+def _forward_pair(shards, tr, x, timestep, context_cond, context_uncond, cond):
+    for sh in shards:
+        sh.begin_pair(x, timestep, context_cond, context_uncond, **cond)
+    run_blocks(shards, tr)
+    sh = shards[0]
+    return _pair_outputs(sh, tr.gather_rows([s.head() for s in shards]).reshape(sh.world, 2 * sh.Ls, -1))
+
+
 def forward_distributed(dit: WanDiT, x, timestep, context, group=None, groups: Optional[int] = None, tea_mode: int = 0,
                         residual: Optional[torch.Tensor] = None, mode: Optional[str] = None, audio_embed_tuple=None, **cond) -> torch.Tensor:
     """model_fn_wan_video(..., use_unified_sequence_parallel=True) for this rank of `group`: every rank passes the same inputs
@@ -390,123 +509,19 @@ def forward_distributed(dit: WanDiT, x, timestep, context, group=None, groups: O
     `residual` — no exchange at all in that forward besides the final all-gather.
     audio_embed_tuple (the talk variant, WanDiT.set_audio): armed for this forward and disarmed after it; a handle armed beforehand
     (model_fn_wan_talk_video) is served as it is.  Every rank projects all frames' audio tokens; its rows attend to their own frames'."""
-    disarm = _armed([dit], audio_embed_tuple)
-    try:
-        return _forward_distributed(dit, x, timestep, context, group, groups, tea_mode, residual, mode, **cond)
-    finally:
-        disarm()
-
-
-def _forward_distributed(dit: WanDiT, x, timestep, context, group, groups, tea_mode, residual, mode, **cond) -> torch.Tensor:
-    rank, world = dist.get_rank(group), dist.get_world_size(group)
-    sh = SequenceShard(dit, rank, world, groups, mode)
-    sh.begin(x, timestep, context, **cond)
-    b, G = sh.buf, sh.G
-    if tea_mode == 2:
-        sh.tea(2, residual)
-        return sh.unpatchify(all_gather_rows(sh.head(), group))
-    if tea_mode == 1:
-        sh.tea(0)
-    if sh.mode == "gather":
-        for layer in range(dit.num_layers):
-            sh.block_v_rows(layer)                                   # V^T first: its all-gather runs under the q | k projection and RoPE
-            hv = _all_gather_into(b.vt_all, b.vt, group, True)
-            sh.block_qk_rows(layer)
-            hk = _all_gather_into(b.k_all, b.k, group, True)
-            for h_ in (hv, hk):
-                if h_ is not None:
-                    h_.wait()
-            sh.attention_rows()
-            sh.block_rest_rows(layer)
-        if tea_mode == 1:
-            sh.tea(1, residual)
-        return sh.unpatchify(all_gather_rows(sh.head(), group))
-    _blocks_distributed(sh, group)
-    if tea_mode == 1:
-        sh.tea(1, residual)
-    return sh.unpatchify(all_gather_rows(sh.head(), group))
+    shard = SequenceShard(dit, dist.get_rank(group), dist.get_world_size(group), groups, mode)
+    return _forward([shard], GroupTransport(group), x, timestep, context, tea_mode, [residual], audio_embed_tuple, cond)
 
 
 def forward_local(dits: Sequence[WanDiT], x, timestep, context, groups: Optional[int] = None, mode: Optional[str] = None,
-                  audio_embed_tuple=None, **cond) -> torch.Tensor:
+                  audio_embed_tuple=None, tea_mode: int = 0, residual: Optional[Sequence[torch.Tensor]] = None, **cond) -> torch.Tensor:
     """The same schedule with P = len(dits) shards in ONE process (each shard needs its own handle: a handle holds one
     workspace); the exchanges are device copies between the shards' buffers.  For tests and for measuring what the schedule costs
     besides the transport on a single GPU (tools/sp_overhead.py, tools/talk_sp_timing.py).  audio_embed_tuple: every shard's handle is armed
-    with the same windows for this forward (the talk variant) and disarmed after it."""
-    disarm = _armed(dits, audio_embed_tuple)
-    try:
-        return _forward_local(dits, x, timestep, context, groups, mode, **cond)
-    finally:
-        disarm()
-
-
-def _forward_local(dits: Sequence[WanDiT], x, timestep, context, groups, mode, **cond) -> torch.Tensor:
-    P = len(dits)
-    shards = [SequenceShard(d, r, P, groups, mode) for r, d in enumerate(dits)]
-    for sh in shards:
-        sh.begin(x, timestep, context, **cond)
-    G = shards[0].G
-    if shards[0].mode == "gather":
-        for layer in range(dits[0].num_layers):
-            for sh in shards:
-                sh.block_v_rows(layer)                               # the split form forward_distributed uses (V^T leaves first)
-                sh.block_qk_rows(layer)
-            for sj in shards:
-                for i, si in enumerate(shards):
-                    sj.buf.k_all[i].copy_(si.buf.k)
-                    sj.buf.vt_all[i].copy_(si.buf.vt)
-            for sh in shards:
-                sh.attention_rows()
-                sh.block_rest_rows(layer)
-        rows = torch.cat([sh.head() for sh in shards], dim=0)
-        return shards[0].unpatchify(rows)
-    for layer in range(dits[0].num_layers):
-        for sh in shards:
-            sh.block_qkv(layer)
-        for j, sj in enumerate(shards):                 # rank j receives piece j of every rank i
-            for i, si in enumerate(shards):
-                sj.buf.vt_recv[i].copy_(si.buf.vt_send[j])
-                sj.buf.qk_recv[:, :, i].copy_(si.buf.qk_send[:, :, j])
-        for sh in shards:
-            sh.unpack_v()
-            for g in range(G):
-                sh.attention(g)
-        for j, sj in enumerate(shards):
-            for i, si in enumerate(shards):
-                sj.buf.o_recv[:, i].copy_(si.buf.o_send[:, j])
-        for sh in shards:
-            sh.block_rest(layer)
-    rows = torch.cat([sh.head() for sh in shards], dim=0)
-    return shards[0].unpatchify(rows)
-
-
-def _pair_outputs(sh: SequenceShard, rows_all: torch.Tensor):
-    """rows_all [P, 2 Ls, ld] (every rank's stacked head rows, rank-major) -> (cond, uncond) latents."""
-    P, Ls = rows_all.shape[0], sh.Ls
-    return tuple(sh.unpatchify(rows_all[:, br * Ls:(br + 1) * Ls].reshape(P * Ls, -1)) for br in range(2))
-
-
-def _blocks_distributed(sh: SequenceShard, group) -> None:
-    """The block loop of the Ulysses mode for this rank (one branch or a stacked pair: the same exchanges, pieces nb x as long)."""
-    b, G = sh.buf, sh.G
-    for layer in range(sh.dit.num_layers):
-        sh.block_qkv(layer)
-        wv = _exchange(b.vt_recv, b.vt_send, group, True)
-        wq = [(_exchange(b.qk_recv[0, g], b.qk_send[0, g], group, True), _exchange(b.qk_recv[1, g], b.qk_send[1, g], group, True)) for g in range(G)]
-        if wv is not None:
-            wv.wait()
-        sh.unpack_v()
-        wo = []
-        for g in range(G):
-            for w_ in wq[g]:
-                if w_ is not None:
-                    w_.wait()
-            sh.attention(g)
-            wo.append(_exchange(b.o_recv[g], b.o_send[g], group, True))
-        for w_ in wo:
-            if w_ is not None:
-                w_.wait()
-        sh.block_rest(layer)
+    with the same windows for this forward (the talk variant) and disarmed after it.  tea_mode as forward_distributed; residual: one [Ls, dim]
+    tensor per shard."""
+    shards = [SequenceShard(d, r, len(dits), groups, mode) for r, d in enumerate(dits)]
+    return _forward(shards, LocalTransport(), x, timestep, context, tea_mode, residual, audio_embed_tuple, cond)
 
 
 def forward_distributed_pair(dit: WanDiT, x, timestep, context_cond, context_uncond, group=None, groups: Optional[int] = None, **cond):
@@ -515,37 +530,11 @@ def forward_distributed_pair(dit: WanDiT, x, timestep, context_cond, context_unc
     pieces, and no rank waits for another's noise prediction — each rank ends with both.  Returns (noise_pred_cond, noise_pred_uncond), full latents on
     every rank; bit-identical to two forward_distributed calls with the key axis in one piece and to WanDiT.forward_cfg_pair on one rank (at P = 4 of the
     1.3B model the doubled head count makes the attention's rounds whole, so no key-axis cut is taken at all).  Ulysses mode; context cache on."""
-    rank, world = dist.get_rank(group), dist.get_world_size(group)
-    sh = SequenceShard(dit, rank, world, groups, "ulysses")
-    sh.begin_pair(x, timestep, context_cond, context_uncond, **cond)
-    _blocks_distributed(sh, group)
-    rows = sh.head()
-    gathered = all_gather_rows(rows, group).reshape(world, 2 * sh.Ls, -1)
-    return _pair_outputs(sh, gathered)
+    shard = SequenceShard(dit, dist.get_rank(group), dist.get_world_size(group), groups, "ulysses")
+    return _forward_pair([shard], GroupTransport(group), x, timestep, context_cond, context_uncond, cond)
 
 
 def forward_local_pair(dits: Sequence[WanDiT], x, timestep, context_cond, context_uncond, groups: Optional[int] = None, **cond):
     """forward_distributed_pair's schedule with P = len(dits) shards in ONE process (device copies for the exchanges): tests, tools/sp_overhead.py."""
-    P = len(dits)
-    shards = [SequenceShard(d, r, P, groups, "ulysses") for r, d in enumerate(dits)]
-    for sh in shards:
-        sh.begin_pair(x, timestep, context_cond, context_uncond, **cond)
-    G = shards[0].G
-    for layer in range(dits[0].num_layers):
-        for sh in shards:
-            sh.block_qkv(layer)
-        for j, sj in enumerate(shards):
-            for i, si in enumerate(shards):
-                sj.buf.vt_recv[i].copy_(si.buf.vt_send[j])
-                sj.buf.qk_recv[:, :, i].copy_(si.buf.qk_send[:, :, j])
-        for sh in shards:
-            sh.unpack_v()
-            for g in range(G):
-                sh.attention(g)
-        for j, sj in enumerate(shards):
-            for i, si in enumerate(shards):
-                sj.buf.o_recv[:, i].copy_(si.buf.o_send[:, j])
-        for sh in shards:
-            sh.block_rest(layer)
-    rows = torch.stack([sh.head() for sh in shards], dim=0)
-    return _pair_outputs(shards[0], rows)
+    shards = [SequenceShard(d, r, len(dits), groups, "ulysses") for r, d in enumerate(dits)]
+    return _forward_pair(shards, LocalTransport(), x, timestep, context_cond, context_uncond, cond)

@@ -1,7 +1,9 @@
-"""-m gpu: sequence-parallel (Ulysses) forward, SURVEY §8e axis 3.  P shards run in one process on one GPU with the all-to-all
-simulated by in-process gathers (svi_hip.sequence_parallel.forward_local): every kernel, row offset and head-group layout of the
-multi-rank path is exercised; only the transport differs (tests/test_dist_gloo.py covers that over gloo).  Expected: the same
-bits as the single-rank forward — each row / head sees the same operands in the same order."""
+"""-m gpu: sequence-parallel (Ulysses) forward, SURVEY §8e axis 3.  P shards run in one process on one GPU
+(svi_hip.sequence_parallel.forward_local): every kernel, row offset and head-group layout of the multi-rank path is exercised, by the
+very block schedule a rank of a process group runs (sequence_parallel.ulysses_blocks / gather_blocks, written once; its order is pinned
+in tests/test_sp_schedule.py) — only the transport differs: device copies here, collectives there (the across-process tests below run
+them over gloo, tests/test_dist_gloo.py the layout algebra).  Expected: the same bits as the single-rank forward — each row / head
+sees the same operands in the same order."""
 import numpy as np
 import pytest
 import torch
@@ -231,3 +233,71 @@ def test_forward_distributed_across_processes(world):
     from spawn_util import run_ranks
     res = run_ranks(_dist_worker, world, timeout=300)
     assert sorted(r for r, _, _ in res) == list(range(world)) and all(a and b for _, a, b in res), res
+
+
+def _dist_groups_worker(rank, world, port, queue):
+    import os
+    import torch.distributed as dist
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        import svi_hip
+        from svi_hip import sequence_parallel as sp
+        torch.cuda.set_device(0)
+        m = handles(svi_hip, WIDE_T2V, 900, 1)[0]
+        x = dev(synth.randn(901, 1, 16, 2, 16, 24))                    # 192 tokens, 4 heads: 2 heads per rank = 2 groups of one
+        ca, cb = dev(synth.text_context(902, 24, 64, 17)), dev(synth.text_context(903, 24, 64, 9))
+        t = torch.tensor([712.5])
+        want_a, want_b = m.forward(x, t, ca).clone(), m.forward(x, t, cb).clone()
+        ok_groups = bool(torch.equal(sp.forward_distributed(m, x, t, ca, groups=2), want_a))
+        gathered = sp.forward_distributed(m, x, t, ca, mode="gather")
+        rel = float((gathered.float() - want_a.float()).norm() / want_a.float().norm())
+        m.context_cache(True)
+        try:
+            got_a, got_b = sp.forward_distributed_pair(m, x, t, ca, cb, groups=2)
+            ok_pair = bool(torch.equal(got_a, want_a)) and bool(torch.equal(got_b, want_b))
+        finally:
+            m.context_cache(False)
+        queue.put((rank, ok_groups, ok_pair, rel))
+    finally:
+        dist.destroy_process_group()
+
+
+def test_pipelined_head_groups_and_gather_mode_across_processes():
+    """The G = 2 pipeline (all q | k exchanges up front, per group wait / attend / send the output) and the split gather order over a real
+    process group, 2 ranks: forward_distributed(groups=2) and forward_distributed_pair(groups=2) give the single-rank bits, gather mode
+    meets the attention tolerance of test_gather_mode_serves_head_counts_that_do_not_divide."""
+    from spawn_util import run_ranks
+    res = run_ranks(_dist_groups_worker, 2, timeout=300)
+    assert sorted(r[0] for r in res) == [0, 1] and all(a and b for _, a, b, _ in res), res
+    assert all(rel < 3e-3 for *_, rel in res), res
+
+
+@pytest.mark.parametrize("P,G,mode", [(2, 2, "ulysses"), (3, 1, "gather")])
+def test_teacache_on_in_process_shards(P, G, mode):
+    """TeaCache through the shared schedule (forward_local(tea_mode=, residual=)): a computed step that also writes every shard's residual rows,
+    then a skipped step that adds them, against the single-rank TeaCache path (model_fn_wan_video with a TeaCache whose huge threshold makes
+    step 1 a skip).  Ulysses: the same bits, residual included; gather: within the attention tolerance (3e-3 on the forward)."""
+    import svi_hip
+    from svi_hip import sequence_parallel as sp
+    f, h, w = 2, 4, 6
+    ms = handles(svi_hip, WIDE_T2V, 900, P + 1)
+    x = dev(synth.randn(901, 1, 16, f, 2 * h, 2 * w))
+    ctx = dev(synth.text_context(902, 24, 64, 17))
+    t1, t2 = torch.tensor([500.0]).cuda(), torch.tensor([500.01]).cuda()
+    tc = svi_hip.TeaCache(5, 1e9, "Wan2.1-T2V-1.3B")
+    want1 = svi_hip.model_fn_wan_video(ms[-1], x, t1, ctx, tea_cache=tc).clone()
+    x2 = (x.float() + 0.05 * want1.float()).to(torch.bfloat16)
+    want2 = svi_hip.model_fn_wan_video(ms[-1], x2, t2, ctx, tea_cache=tc).clone()
+    assert tc.step == 2 and tc.accumulated_rel_l1_distance != 0       # step 1 skipped: a computed step empties the sum
+    res = [torch.empty((f * h * w // P, 512), dtype=torch.bfloat16, device="cuda") for _ in range(P)]
+    got1 = sp.forward_local(ms[:P], x, t1, ctx, groups=G, mode=mode, tea_mode=1, residual=res)
+    got2 = sp.forward_local(ms[:P], x2, t2, ctx, groups=G, mode=mode, tea_mode=2, residual=res)
+    assert torch.isfinite(got1.float()).all() and torch.isfinite(got2.float()).all()
+    if mode == "ulysses":
+        assert torch.equal(got1, want1) and torch.equal(torch.cat(res), tc.previous_residual[0]) and torch.equal(got2, want2)
+    else:
+        for got, want in ((got1, want1), (got2, want2)):
+            rel = float((got.float() - want.float()).norm() / want.float().norm())
+            assert rel < 3e-3, rel

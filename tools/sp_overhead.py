@@ -41,6 +41,14 @@ def tags(fn):
     _lib.prof_enable(False)
     return out
 base_tags = tags(lambda: plain.forward(x, t, ctx))
+class CopiesOnly:
+    """A shard's cached exchange buffers with every stage a no-op: the schedule run on these makes its transport calls and nothing else."""
+    mode, dit = "ulysses", plain
+    def __init__(self, buf, G): self.buf, self.G = buf, G
+    def __getattr__(self, stage): return lambda *a: None
+def copies(hs, G, nb):
+    """the simulated transport, timed alone: forward_local[_pair]'s own schedule and LocalTransport on the buffers the forward left in the cache"""
+    sp.run_blocks([CopiesOnly(b, G) for m in hs for k, b in m._sp_buffers.items() if k[3] == G and k[5] == nb], sp.LocalTransport())
 if "pair" in sys.argv[1:]:
     ctx2 = torch.randn((1, 512, 4096), generator=g, device=dev).to(torch.bfloat16)
     ctx[:, 64:] = 0; ctx2[:, 32:] = 0
@@ -55,13 +63,7 @@ if "pair" in sys.argv[1:]:
         ms2 = timeit(two)
         for G in sorted({1, sp.head_groups(12 // P, 32760, 2)}):
             msp = timeit(lambda: sp.forward_local_pair(hs, x, t, ctx, ctx2, groups=G))
-            def copies(nb):
-                bufs = [m._sp_buffers[k] for m in hs for k in m._sp_buffers if k[3] == (G if nb == 2 else G1) and k[5] == nb]
-                for _ in range(layers):
-                    for j, bj in enumerate(bufs):
-                        for i, bi in enumerate(bufs):
-                            bj.vt_recv[i].copy_(bi.vt_send[j]); bj.qk_recv[:, :, i].copy_(bi.qk_send[:, :, j]); bj.o_recv[:, i].copy_(bi.o_send[:, j])
-            cp1, cp2 = timeit(lambda: copies(1)), timeit(lambda: copies(2))
+            cp1, cp2 = timeit(lambda: copies(hs, G1, 1)), timeit(lambda: copies(hs, G, 2))
             r_two, r_pair = (ms2 - 2 * cp1) / P, (msp - cp2) / P
             print(f"P={P} G={G}: per rank compute + unpack per STEP: two shard forwards {r_two:.1f} ms ({r_two / (pair_base / P) - 1:+.1%} over the ideal 1/P of the single-rank "
                   f"stacked pair), stacked pair on the shard {r_pair:.1f} ms ({r_pair / (pair_base / P) - 1:+.1%}); simulated transport {2 * cp1:.1f} / {cp2:.1f} ms")
@@ -75,14 +77,7 @@ for P in (2, 4, 6):
     for m in hs: m.context_cache(True)
     for G in sorted({1, sp.head_groups(12 // P, 32760)}):
         ms = timeit(lambda: sp.forward_local(hs, x, t, ctx, groups=G))
-        # the simulated transport: the same device copies forward_local makes between the shards' buffers, timed alone
-        bufs = [m._sp_buffers[k] for m in hs for k in m._sp_buffers if k[3] == G]
-        def copies():
-            for _ in range(layers):
-                for j, bj in enumerate(bufs):
-                    for i, bi in enumerate(bufs):
-                        bj.vt_recv[i].copy_(bi.vt_send[j]); bj.qk_recv[:, :, i].copy_(bi.qk_send[:, :, j]); bj.o_recv[:, i].copy_(bi.o_send[:, j])
-        cp = timeit(copies)
+        cp = timeit(lambda: copies(hs, G, 1))
         per_rank = (ms - cp) / P
         print(f"P={P} G={G}: all shards back to back {ms:.1f} ms, of which simulated transport {cp:.1f} ms -> per rank compute + unpack {per_rank:.1f} ms "
               f"({per_rank / (base / P) - 1:+.1%} over an ideal 1/P split); exchange volume per block and rank {(32760 // P) * (1536 // P) * (P - 1) * 2 * 4 / 1e6:.1f} MB")

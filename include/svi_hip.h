@@ -421,6 +421,27 @@ svi_status svi_vae_tiled_decode(svi_vae* h, const float* latents, float* video, 
 svi_status svi_vae_tiled_encode(svi_vae* h, const float* video, float* latents, int32_t T, int32_t H, int32_t W,
                                 int32_t size_h, int32_t size_w, int32_t stride_h, int32_t stride_w, svi_stream stream);
 
+/* Exact spatial split of the decode, for the multi-GPU latency modes: the decoder's middle block attends over a whole frame, everything behind it
+ * is local, so a part runs conv2 / conv1 / middle on the whole latent frame, crops the activation to its owned rectangle plus a halo, and runs the
+ * four upsampling stages and the head on the crop, trimming the crop again after every upsample block.  Unlike the blended tiling this computes
+ * what svi_vae_decode computes (up to the summation order of whichever convolution kernel a cropped shape selects).
+ * svi_vae_split_plan (host arithmetic, no device): part = i * parts_w + j of a parts_h x parts_w split of the hh x ww latent grid; cuts sit at
+ *   floor(i hh / parts_h), floor(j ww / parts_w).  out24 = {owned latent rectangle h0, h1, w0, w1 | halo per side entering stages 0-3, in pixels of
+ *   that stage's resolution (latent x 1, 2, 4, 8), derived from the decoder's layer table | the rectangle entering stage 0 (h0, h1, w0, w1, stage
+ *   resolution) | stage 1 | stage 2 | stage 3}: the owned rectangle scaled, grown by the halo along the dimensions that are cut, clamped at the
+ *   image border (where the kernels' zero padding is the real padding).  A 1 x 1 split reports zero halos.
+ * svi_vae_decode_part: latents f32 [16, T, hh, ww] (whole) -> the part's owned pixels of the clamped video.  `video` points at where the owned
+ *   window's first pixel (channel 0, frame 0) goes; pixel (c, t, y, x) of the window is written at ((c T' + t) video_ld_h + y) video_ld_w + x,
+ *   T' = 1 + 4 (T - 1).  A full frame: video_ld_h = 8 hh, video_ld_w = 8 ww and `video` offset to the window; a tight buffer: the window's own
+ *   size.  Nothing else is written.  A 1 x 1 split into a full frame is svi_vae_decode.
+ * svi_vae_decode_planned: the same with the caller's plan (svi_vae_split_plan's layout; the halo entries are not read).  The rectangles are held
+ *   to what keeps every crop inside its tensor, not to the halo: a plan with a short halo decodes with errors next to the cuts. */
+svi_status svi_vae_split_plan(int32_t hh, int32_t ww, int32_t parts_h, int32_t parts_w, int32_t part, int32_t* out24);
+svi_status svi_vae_decode_part(svi_vae* h, const float* latents, float* video, int32_t T, int32_t hh, int32_t ww, int32_t parts_h, int32_t parts_w,
+                               int32_t part, int32_t video_ld_h, int32_t video_ld_w, svi_stream stream);
+svi_status svi_vae_decode_planned(svi_vae* h, const float* latents, float* video, int32_t T, int32_t hh, int32_t ww, const int32_t* plan24,
+                                  int32_t video_ld_h, int32_t video_ld_w, svi_stream stream);
+
 /* ------------------------------------------------------------------ dance variant: pose embedder ------- */
 /* The `dwpose_embedding` of SVIDanceVideoPipeline (pipelines/svi_video_dance.py:255-269): seven fp32 Conv3d layers with SiLU between
  * them, 3 -> hidden (16) channels at full resolution down to dim channels at the DiT's token grid.  svi_pose_forward also does what

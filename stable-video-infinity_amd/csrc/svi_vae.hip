@@ -2064,6 +2064,185 @@ svi_status decode_graph(svi_vae* h, const float* latents, float* video, int T, i
     return SVI_OK;
 }
 
+// ---- exact spatial split of the decode (svi_vae_split_plan / svi_vae_decode_part) --------------------------------------------------
+// The middle block attends over a whole frame, everything behind it is local (3-tap convolutions, per-pixel norms, nearest x2, 1x1
+// shortcuts).  A part therefore runs conv2 / conv1 / middle on the whole latent frame, then crops the activation to its owned rectangle
+// plus a halo and runs the four stages and the head on the crop.  The halo entering each stage is what the layers BEHIND that point can
+// still reach, so the crop is trimmed again after every upsample block instead of carrying the first halo through as 8x as many pixels.
+struct SplitPlan {
+    int own[4];                      // owned latent rectangle {h0, h1, w0, w1}
+    int halo[4];                     // per side, in pixels of the stage's resolution (latent x 2^s)
+    int pad[4][4];                   // rectangle entering stage s, in that stage's resolution: owned x 2^s grown by halo[s], clamped to the image
+};
+
+// The decoder behind the middle block, as decode_graph walks it: three residual blocks per stage, an upsample block behind stages 0-2.
+struct DecStage { std::string res[3], up; bool temporal; };
+static void decoder_stages(DecStage out[4]) {
+    const std::string d = "model.decoder.";
+    const bool tup[3] = {true, true, false};
+    int idx = 0;
+    for (int i = 0; i < 4; ++i) {
+        for (int r = 0; r < 3; ++r) out[i].res[r] = d + "upsamples." + std::to_string(idx++) + ".";
+        out[i].up = i != 3 ? d + "upsamples." + std::to_string(idx++) + "." : std::string();
+        out[i].temporal = i != 3 && tup[i];
+    }
+}
+
+// How far (pixels per side) the layers behind the entry of each stage reach, from the architecture table: walked backwards from the
+// output, a k-tap convolution adds k / 2, a residual block the larger of its two convolutions in a row and its shortcut, and the
+// nearest x2 upsample in front of a resample convolution halves what is needed behind it, rounded up.
+static void decoder_halos(int halo[4]) {
+    static const svi_vae* arch = [] { svi_vae* a = new svi_vae(); declare_architecture(a); return a; }();
+    auto reach = [&](const std::string& name) {
+        auto c = arch->convs.find(name);
+        return c == arch->convs.end() ? 0 : std::max(c->second.kh, c->second.kw) / 2;
+    };
+    DecStage stg[4];
+    decoder_stages(stg);
+    int need = reach("model.decoder.head.2");
+    for (int s = 3; s >= 0; --s) {
+        if (s != 3) {
+            need += reach(stg[s].up + "resample.1");
+            need = (need + 1) / 2;
+            need += reach(stg[s].up + "time_conv");
+        }
+        for (int r = 2; r >= 0; --r)
+            need += std::max(reach(stg[s].res[r] + "residual.2") + reach(stg[s].res[r] + "residual.6"), reach(stg[s].res[r] + "shortcut"));
+        halo[s] = need;
+    }
+}
+
+static svi_status split_plan(int hh, int ww, int parts_h, int parts_w, int part, SplitPlan* pl) {
+    SVI_REQUIRE(hh > 0 && ww > 0 && parts_h > 0 && parts_w > 0, "svi_vae_split_plan: the grid and the split must be positive (got %d x %d in %d x %d parts)", hh, ww, parts_h, parts_w);
+    SVI_REQUIRE(hh <= (1 << 20) && ww <= (1 << 20), "svi_vae_split_plan: latent grid %d x %d is too large", hh, ww);
+    SVI_REQUIRE(parts_h <= hh && parts_w <= ww, "svi_vae_split_plan: %d x %d parts of a %d x %d latent grid would leave a part without a pixel", parts_h, parts_w, hh, ww);
+    SVI_REQUIRE(part >= 0 && part < parts_h * parts_w, "svi_vae_split_plan: part %d is outside the %d x %d split", part, parts_h, parts_w);
+    const int i = part / parts_w, j = part % parts_w;
+    pl->own[0] = (int)((long)i * hh / parts_h); pl->own[1] = (int)((long)(i + 1) * hh / parts_h);
+    pl->own[2] = (int)((long)j * ww / parts_w); pl->own[3] = (int)((long)(j + 1) * ww / parts_w);
+    decoder_halos(pl->halo);
+    for (int s = 0; s < 4; ++s) {
+        const int hal_h = parts_h > 1 ? pl->halo[s] : 0, hal_w = parts_w > 1 ? pl->halo[s] : 0;
+        pl->pad[s][0] = std::max((pl->own[0] << s) - hal_h, 0); pl->pad[s][1] = std::min((pl->own[1] << s) + hal_h, hh << s);
+        pl->pad[s][2] = std::max((pl->own[2] << s) - hal_w, 0); pl->pad[s][3] = std::min((pl->own[3] << s) + hal_w, ww << s);
+    }
+    if (parts_h * parts_w == 1) for (int s = 0; s < 4; ++s) pl->halo[s] = 0;
+    return SVI_OK;
+}
+
+// A caller's plan may be anything: hold it to what keeps every crop inside the tensor it is cut from (not to the halo, which is the
+// planner's business).
+static svi_status split_plan_check(const SplitPlan& pl, int hh, int ww) {
+    SVI_REQUIRE(hh <= (1 << 20) && ww <= (1 << 20), "svi_vae_decode_planned: latent grid %d x %d is too large", hh, ww);
+    SVI_REQUIRE(0 <= pl.own[0] && pl.own[0] < pl.own[1] && pl.own[1] <= hh && 0 <= pl.own[2] && pl.own[2] < pl.own[3] && pl.own[3] <= ww,
+                "svi_vae_decode_planned: owned rectangle [%d, %d) x [%d, %d) is not inside the %d x %d latent grid", pl.own[0], pl.own[1], pl.own[2], pl.own[3], hh, ww);
+    for (int s = 0; s < 4; ++s) {
+        const int* r = pl.pad[s];
+        SVI_REQUIRE(0 <= r[0] && r[0] <= (pl.own[0] << s) && (pl.own[1] << s) <= r[1] && r[1] <= (hh << s) &&
+                    0 <= r[2] && r[2] <= (pl.own[2] << s) && (pl.own[3] << s) <= r[3] && r[3] <= (ww << s),
+                    "svi_vae_decode_planned: stage %d rectangle [%d, %d) x [%d, %d) does not lie between the owned rectangle and the image", s, r[0], r[1], r[2], r[3]);
+        if (s > 0) {
+            const int* q = pl.pad[s - 1];
+            SVI_REQUIRE(2 * q[0] <= r[0] && r[1] <= 2 * q[1] && 2 * q[2] <= r[2] && r[3] <= 2 * q[3],
+                        "svi_vae_decode_planned: stage %d rectangle is not inside the upsampled stage %d rectangle", s, s - 1);
+        }
+    }
+    return SVI_OK;
+}
+
+// channels-last [T, H, W, C] -> its window [T, h, w, C] at (y0, x0), four channels per thread; every offset is 64-bit
+__global__ __launch_bounds__(256) void crop_kernel(const float4* __restrict__ in, float4* __restrict__ out, long n, int H, int W, int c4, int y0, int x0, int hc, int wc) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int c = (int)(i % c4);
+    long sp = i / c4;
+    const int x = (int)(sp % wc); sp /= wc;
+    const int y = (int)(sp % hc);
+    const long t = sp / hc;
+    out[i] = in[((t * H + y0 + y) * W + x0 + x) * c4 + c];
+}
+// channels-last [T, H, W, ld] window (y0, x0, oh, ow) -> video[c][t][y][x] at the caller's pitches (ld_h rows per plane, ld_w elements per
+// row), clamped to [-1,1]; `v` is where the window's first pixel goes
+__global__ __launch_bounds__(256) void video_out_part_kernel(const float* __restrict__ in, int ld, float* __restrict__ v, long n, int T, int H, int W, int y0, int x0,
+                                                             int oh, int ow, long ld_h, long ld_w) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int x = (int)(i % ow);
+    long r = i / ow;
+    const int y = (int)(r % oh); r /= oh;
+    const long t = r % T;
+    const long c = r / T;
+    v[((c * T + t) * ld_h + y) * ld_w + x] = fminf(fmaxf(in[((t * H + y0 + y) * W + x0 + x) * ld + c], -1.f), 1.f);
+}
+
+// x <- its window; consumes x.  A window that is the whole tensor moves nothing.
+svi_status crop_t(svi_vae* h, Tens* x, int y0, int x0, int hc, int wc, hipStream_t st) {
+    SVI_REQUIRE(y0 >= 0 && x0 >= 0 && hc > 0 && wc > 0 && y0 + hc <= x->H && x0 + wc <= x->W, "VAE crop: window %d+%d x %d+%d leaves the %d x %d activation", y0, hc, x0, wc, x->H, x->W);
+    if (hc == x->H && wc == x->W) return SVI_OK;
+    SVI_REQUIRE(x->plane_scale == 0.f && x->C % 4 == 0, "VAE crop: needs an fp32 activation with a multiple of 4 channels (C=%d)", x->C);
+    Tens out = alloc_t(h, x->T, hc, wc, x->C);
+    NEED(out);
+    out.bound = x->bound;
+    if (!h->dry) {
+        const long n = out.elems() / 4;
+        SVI_REQUIRE((n + 255) / 256 < (1L << 31), "VAE crop: %ld elements need more workgroups than one launch has", out.elems());
+        SviProfScope _p(PROF_VAE_OTHER, st);
+        hipLaunchKernelGGL(crop_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, reinterpret_cast<const float4*>(x->p), reinterpret_cast<float4*>(out.p), n,
+                           x->H, x->W, x->C / 4, y0, x0, hc, wc);
+        SVI_LAUNCH_CHECK();
+    }
+    free_t(h, *x);
+    *x = out;
+    return SVI_OK;
+}
+
+svi_status decode_part_graph(svi_vae* h, const float* latents, float* video, int T, int hh, int ww, const SplitPlan& pl, long ld_h, long ld_w, hipStream_t st) {
+    const std::string d = "model.decoder.";
+    Tens z = alloc_t(h, T, hh, ww, 16);
+    NEED(z);
+    if (!h->dry) {
+        const long n = (long)T * hh * ww * 16;
+        SVI_REQUIRE((n + 255) / 256 < (1L << 31), "svi_vae_decode_part: the latent is too large for one launch");
+        hipLaunchKernelGGL(latent_in_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, latents, z.p, (long)T * hh * ww, h->consts, h->consts + 16);
+        SVI_LAUNCH_CHECK();
+    }
+    Tens x, t2;
+    SVI_TRY(conv_layer(h, "model.conv2", z, &t2, st));
+    free_t(h, z);
+    SVI_TRY(conv_layer(h, d + "conv1", t2, &x, st));
+    free_t(h, t2);
+    SVI_TRY(res_block(h, d + "middle.0.", &x, st));
+    SVI_TRY(attn_block(h, d + "middle.1.", &x, st));
+    SVI_TRY(res_block(h, d + "middle.2.", &x, st));
+    DecStage stg[4];
+    decoder_stages(stg);
+    SVI_TRY(crop_t(h, &x, pl.pad[0][0], pl.pad[0][2], pl.pad[0][1] - pl.pad[0][0], pl.pad[0][3] - pl.pad[0][2], st));
+    for (int i = 0; i < 4; ++i) {
+        for (int r = 0; r < 3; ++r) SVI_TRY(res_block(h, stg[i].res[r], &x, st));
+        if (i != 3) {
+            SVI_TRY(upsample_block(h, stg[i].up, &x, stg[i].temporal, st));
+            const int* q = pl.pad[i];            // x now covers 2 q; trim it to what the stages behind still need
+            const int* r = pl.pad[i + 1];
+            SVI_TRY(crop_t(h, &x, r[0] - 2 * q[0], r[2] - 2 * q[2], r[1] - r[0], r[3] - r[2], st));
+        }
+    }
+    Tens n, rgb;
+    SVI_TRY(norm_act(h, d + "head.0.gamma", x, &n, 1, st, planes_scale_for(h, d + "head.2", d + "head.0.gamma", x)));
+    free_t(h, x);
+    SVI_TRY(conv_layer(h, d + "head.2", n, &rgb, st));
+    free_t(h, n);
+    if (!h->dry) {
+        const int y0 = 8 * pl.own[0] - pl.pad[3][0], x0 = 8 * pl.own[2] - pl.pad[3][2], oh = 8 * (pl.own[1] - pl.own[0]), ow = 8 * (pl.own[3] - pl.own[2]);
+        SVI_REQUIRE(y0 >= 0 && x0 >= 0 && y0 + oh <= rgb.H && x0 + ow <= rgb.W, "svi_vae_decode_part: the owned window leaves the decoded crop");
+        const long cnt = 3L * rgb.T * oh * ow;
+        SVI_REQUIRE((cnt + 255) / 256 < (1L << 31), "svi_vae_decode_part: the owned window is too large for one launch");
+        hipLaunchKernelGGL(video_out_part_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, rgb.p, rgb.C, video, cnt, rgb.T, rgb.H, rgb.W, y0, x0, oh, ow, ld_h, ld_w);
+        SVI_LAUNCH_CHECK();
+    }
+    free_t(h, rgb);
+    return SVI_OK;
+}
+
 svi_status encode_graph(svi_vae* h, const float* video, float* latents, int T, int H, int W, hipStream_t st) {
     const std::string e = "model.encoder.";
     Tens v = alloc_t(h, T, H, W, 4);
@@ -2263,6 +2442,52 @@ extern "C" svi_status svi_vae_decode(svi_vae* h, const float* latents, float* vi
     SVI_TRY(ensure_pool(h, h->dry_max));
     h->slot_used.assign(h->nslots, 0);
     return decode_graph(h, latents, video, T, hh, ww, st);
+}
+
+// out24 = {owned h0, h1, w0, w1 | halo of stages 0-3 | stage 0 rectangle h0, h1, w0, w1 | stage 1 | stage 2 | stage 3}.  Host arithmetic only.
+extern "C" svi_status svi_vae_split_plan(int32_t hh, int32_t ww, int32_t parts_h, int32_t parts_w, int32_t part, int32_t* out24) {
+    SVI_REQUIRE(out24, "svi_vae_split_plan: null argument");
+    SplitPlan pl{};
+    SVI_TRY(split_plan(hh, ww, parts_h, parts_w, part, &pl));
+    for (int k = 0; k < 4; ++k) { out24[k] = pl.own[k]; out24[4 + k] = pl.halo[k]; }
+    for (int s = 0; s < 4; ++s) for (int k = 0; k < 4; ++k) out24[8 + 4 * s + k] = pl.pad[s][k];
+    return SVI_OK;
+}
+
+static svi_status decode_with_plan(svi_vae* h, const float* latents, float* video, int T, int hh, int ww, const SplitPlan& pl, int32_t video_ld_h, int32_t video_ld_w,
+                                   hipStream_t st) {
+    SVI_REQUIRE(video_ld_h >= 8 * (pl.own[1] - pl.own[0]) && video_ld_w >= 8 * (pl.own[3] - pl.own[2]),
+                "svi_vae_decode_part: video pitches %d rows x %d elements are smaller than the owned window %d x %d", video_ld_h, video_ld_w,
+                8 * (pl.own[1] - pl.own[0]), 8 * (pl.own[3] - pl.own[2]));
+    SVI_TRY(vae_prepare(h));
+    h->dry = true; h->dry_max = 0;
+    const svi_status dry = decode_part_graph(h, latents, video, T, hh, ww, pl, video_ld_h, video_ld_w, st);
+    h->dry = false;
+    SVI_TRY(dry);
+    SVI_TRY(ensure_pool(h, h->dry_max));
+    h->slot_used.assign(h->nslots, 0);
+    return decode_part_graph(h, latents, video, T, hh, ww, pl, video_ld_h, video_ld_w, st);
+}
+
+extern "C" svi_status svi_vae_decode_part(svi_vae* h, const float* latents, float* video, int32_t T, int32_t hh, int32_t ww, int32_t parts_h, int32_t parts_w,
+                                          int32_t part, int32_t video_ld_h, int32_t video_ld_w, svi_stream stream) {
+    SVI_REQUIRE(h && latents && video && T > 0 && hh > 0 && ww > 0, "svi_vae_decode_part: bad argument");
+    SVI_REQUIRE_DEVICE(h);
+    SplitPlan pl{};
+    SVI_TRY(split_plan(hh, ww, parts_h, parts_w, part, &pl));
+    if (parts_h * parts_w == 1 && video_ld_h == 8 * hh && video_ld_w == 8 * ww) return svi_vae_decode(h, latents, video, T, hh, ww, stream);
+    return decode_with_plan(h, latents, video, T, hh, ww, pl, video_ld_h, video_ld_w, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" svi_status svi_vae_decode_planned(svi_vae* h, const float* latents, float* video, int32_t T, int32_t hh, int32_t ww, const int32_t* plan24,
+                                             int32_t video_ld_h, int32_t video_ld_w, svi_stream stream) {
+    SVI_REQUIRE(h && latents && video && plan24 && T > 0 && hh > 0 && ww > 0, "svi_vae_decode_planned: bad argument");
+    SVI_REQUIRE_DEVICE(h);
+    SplitPlan pl{};
+    for (int k = 0; k < 4; ++k) { pl.own[k] = plan24[k]; pl.halo[k] = plan24[4 + k]; }
+    for (int s = 0; s < 4; ++s) for (int k = 0; k < 4; ++k) pl.pad[s][k] = plan24[8 + 4 * s + k];
+    SVI_TRY(split_plan_check(pl, hh, ww));
+    return decode_with_plan(h, latents, video, T, hh, ww, pl, video_ld_h, video_ld_w, reinterpret_cast<hipStream_t>(stream));
 }
 
 extern "C" svi_status svi_vae_encode(svi_vae* h, const float* video, float* latents, int32_t T, int32_t H, int32_t W,

@@ -103,6 +103,9 @@ SYMBOLS = [
     ("svi_vae_encode", _i32, [_vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     ("svi_vae_tiled_decode", _i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     ("svi_vae_tiled_encode", _i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    ("svi_vae_split_plan", _i32, [_i32, _i32, _i32, _i32, _i32, C.POINTER(_i32)]),
+    ("svi_vae_decode_part", _i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    ("svi_vae_decode_planned", _i32, [_vp, _vp, _vp, _i32, _i32, _i32, C.POINTER(_i32), _i32, _i32, _vp]),
     ("svi_pose_create", _i32, [_i32, _i32, C.POINTER(_vp)]),
     ("svi_pose_destroy", _i32, [_vp]),
     ("svi_pose_bind_weight", _i32, [_vp, C.c_char_p, _vp, _i32, C.POINTER(_i64), _i32]),
@@ -224,6 +227,14 @@ def vae_tile_order(ord_T: int, ord_Lf: int, ord_G: int) -> list:
     out = (_i64 * (ord_T * ord_Lf))()
     check(lib().svi_vae_tile_order(ord_T, ord_Lf, ord_G, out), "svi_vae_tile_order")
     return list(out)
+
+
+def vae_split_plan(hh: int, ww: int, parts_h: int, parts_w: int, part: int) -> dict:
+    """One part of the exact spatial split of the VAE decode (see include/svi_hip.h): rectangles are (h0, h1, w0, w1); `owned` in latent pixels,
+    `padded[s]` entering decoder stage s in that stage's resolution (latent x 2^s), `halo[s]` per side in the same unit."""
+    out = (_i32 * 24)()
+    check(lib().svi_vae_split_plan(hh, ww, parts_h, parts_w, part, out), "svi_vae_split_plan")
+    return {"owned": tuple(out[0:4]), "halo": tuple(out[4:8]), "padded": [tuple(out[8 + 4 * s:12 + 4 * s]) for s in range(4)]}
 
 
 def prof_select(tags=None) -> None:

@@ -553,8 +553,15 @@ def _hip_wan_pipeline_call(self, *args, **kwargs):
         seen["denoised"] = x.clone() if resident else x
         return ()
 
-    def decode_video(latents, *a, **k):
-        return getattr(cls, "decode_video")(self, seen.get("denoised", latents), *a, **k)
+    def decode_video(latents, *a, vae_split=None, vae_group=None, **k):
+        # vae_split / vae_group: the exact rank split of the decode (WanVideoVAE.decode); the pipeline's own setting (install(vae_split=...)) unless given
+        was = self.__dict__.get("_svi_hip_vae_split")
+        if vae_split is not None or vae_group is not None:
+            self._svi_hip_vae_split = _vae_split_setting(vae_split, vae_group)
+        try:
+            return getattr(cls, "decode_video")(self, seen.get("denoised", latents), *a, **k)
+        finally:
+            self._svi_hip_vae_split = was
 
     shadows = {"encode_prompt": remember("encode_prompt", lambda a, k: "posi" if (k.get("positive", a[1] if len(a) > 1 else True)) else "nega"),
                "prepare_extra_input": remember("prepare_extra_input"), "decode_video": decode_video}
@@ -568,6 +575,17 @@ def _hip_wan_pipeline_call(self, *args, **kwargs):
     finally:
         for name in shadows:
             self.__dict__.pop(name, None)
+
+
+def _vae_split_setting(vae_split, vae_group) -> Optional[dict]:
+    """What install()'s VAE decode passes on to WanVideoVAE.decode: nothing (the default: the whole decode on this rank), or split (+ group)."""
+    if vae_split is None and vae_group is None:
+        return None
+    if vae_split is None:
+        import torch.distributed as dist
+        from .vae import default_vae_split
+        vae_split = default_vae_split(dist.get_world_size(vae_group))
+    return dict(split=tuple(vae_split), group=vae_group)
 
 
 def _route_wan_call(pipe, hip) -> bool:
@@ -681,7 +699,7 @@ def _assert_resident(pipe, hip: WanDiT, full: bool = False) -> None:
         hip.check_module_in_place(dit_module)
 
 
-def install(pipe, vae: bool = True, encoders: bool = True, sampler: bool = True, resident: bool = True):
+def install(pipe, vae: bool = True, encoders: bool = True, sampler: bool = True, resident: bool = True, vae_split=None, vae_group=None):
     """Route `pipe`'s hot path (SVIVideoPipeline / WanVideoPipeline of the reference) through libsvi_hip.
 
     * `model_fn_wan_video` in the pipeline's defining module is replaced by the HIP-backed function
@@ -690,7 +708,9 @@ def install(pipe, vae: bool = True, encoders: bool = True, sampler: bool = True,
       signature — one C call for the two forwards of a step, fused CFG + Euler kernel: the loop bench.py times; a WanVideoPipeline, whose loop is
       inline in `__call__` (wan_video.py:266-278), gets the same loop through `_hip_wan_pipeline_call` (the reference's own `__call__` keeps running
       around it: every line outside the loop is the reference's);
-    * `pipe.vae.encode/decode` are rebound to the HIP VAE (same signatures), when `vae` is true;
+    * `pipe.vae.encode/decode` are rebound to the HIP VAE (same signatures), when `vae` is true; `vae_split` = (parts_h, parts_w) (+ `vae_group`, whose
+      ranks each decode one part; a group alone takes default_vae_split's grid) makes every decode the exact spatial split of WanVideoVAE.decode —
+      off by default; call the pipeline with tiled=False then, the blended tiling and the split exclude each other;
     * `pipe.dit` stays the reference nn.Module: weights are borrowed, so call `install` again (or
       `pipe._svi_hip_dit.rebind()`) after `load_lora_v2`, `.to()` or any offload that moves storage.
     * with `encoders`: the prompter's `text_encoder(ids, mask)` (prompters/wan_prompter.py:109) and `pipe.image_encoder.encode_image`
@@ -723,8 +743,10 @@ def install(pipe, vae: bool = True, encoders: bool = True, sampler: bool = True,
         pipe._svi_hip_vae = hv
         pipe.vae.encode = types.MethodType(lambda self, videos, device=None, tiled=False, tile_size=(34, 34),
                                            tile_stride=(18, 16): hv.encode(videos, device, tiled, tile_size, tile_stride), pipe.vae)
+        pipe._svi_hip_vae_split = _vae_split_setting(vae_split, vae_group)
         pipe.vae.decode = types.MethodType(lambda self, hidden_states, device=None, tiled=False, tile_size=(34, 34),
-                                           tile_stride=(18, 16): hv.decode(hidden_states, device, tiled, tile_size, tile_stride), pipe.vae)
+                                           tile_stride=(18, 16): hv.decode(hidden_states, device, tiled, tile_size, tile_stride,
+                                                                           **(pipe.__dict__.get("_svi_hip_vae_split") or {})), pipe.vae)
     if encoders:
         from .encoders import WanImageEncoder, WanTextEncoder
         te = getattr(pipe, "text_encoder", None)

@@ -19,6 +19,7 @@ import torch
 from . import _lib as L
 from .conditioning import image_condition
 from .pipeline import DenoiseLoop, generate_noise
+from .vae import default_vae_split, latency_group
 
 
 def video_to_u8(video: torch.Tensor) -> torch.Tensor:
@@ -43,12 +44,26 @@ class StreamLoop:
     def __init__(self, dit, vae, clip_encoder: Optional[Callable[[torch.Tensor], torch.Tensor]] = None, num_motion_frames: int = 1,
                  num_frames: int = 81, num_inference_steps: int = 50, cfg_scale: float = 5.0, sigma_shift: float = 5.0,
                  ref_pad_cfg: bool = False, ref_pad_num: int = 0, seed_times: int = 42, tiled: bool = False, tile_size=(30, 52),
-                 tile_stride=(15, 26)):
+                 tile_stride=(15, 26), vae_split=None, vae_group=None, cfg_pair=None, sp_group=None, sequence_parallel: bool = False):
         """tiled / tile_size / tile_stride: the VAE tiling arguments SVIVideoPipeline.__call__ passes to decode_video (svi_video.py:439-441, 515;
-        test_svi.py passes args.tiled, default False).  The conditioning encode is never tiled, as in the reference (:350)."""
+        test_svi.py passes args.tiled, default False).  The conditioning encode is never tiled, as in the reference (:350).
+        vae_split = (parts_h, parts_w) / vae_group: the exact spatial split of every clip's decode (WanVideoVAE.decode): with a group each rank
+        decodes one part, without one all parts run here, one after another.  Off by default.  cfg_pair / sequence_parallel (+ sp_group): the
+        latency modes of DenoiseLoop; the decode then uses that group's ranks too, on default_vae_split's grid unless vae_split names one."""
         if num_motion_frames < 1:
             raise ValueError("an image-conditioned stream hands at least one motion frame from clip to clip (test_svi.py:472-476)")
-        self.loop = DenoiseLoop(dit, resident=True)      # every clip of the stream replays the step graph the first one captured
+        if cfg_pair is not None or sequence_parallel:
+            self.loop = DenoiseLoop(dit, cfg_pair=cfg_pair, sp_group=sp_group, sequence_parallel=sequence_parallel)
+            if vae_group is None and (vae_split is None or tuple(vae_split) != (1, 1)):
+                vae_group = latency_group(self.loop)
+        else:
+            self.loop = DenoiseLoop(dit, resident=True)      # every clip of the stream replays the step graph the first one captured
+        if vae_group is not None and vae_split is None:
+            import torch.distributed as dist
+            vae_split = default_vae_split(dist.get_world_size(vae_group))
+        if vae_split is not None and tiled:
+            raise ValueError("StreamLoop: tiled=True blends overlapping tiles, vae_split is the exact rank split; ask for one of them")
+        self.vae_split = dict(split=tuple(vae_split), group=vae_group) if vae_split is not None else {}
         self.vae, self.clip_encoder = vae, clip_encoder
         self.num_motion_frames, self.num_frames = num_motion_frames, num_frames
         self.steps, self.cfg_scale, self.sigma_shift = num_inference_steps, cfg_scale, sigma_shift
@@ -99,7 +114,7 @@ class StreamLoop:
                 cond["clip_feature"] = cf
             lat = self.loop.sample(lat, ctx_pos, ctx_neg, num_inference_steps=self.steps, cfg_scale=self.cfg_scale,
                                    sigma_shift=self.sigma_shift, **cond)
-            video = self.vae.decode(lat.float(), device="cuda", **self.tiler)[0]  # [3, num_frames, H, W] fp32
+            video = self.vae.decode(lat.float(), device="cuda", **self.tiler, **self.vae_split)[0]  # [3, num_frames, H, W] fp32
             frames = video_to_u8(video)
             self.trace.append(dict(clip=k, seed=seed, motion=motion, y=y, latents=lat, frames=frames))
             motion = frames[-self.num_motion_frames:]

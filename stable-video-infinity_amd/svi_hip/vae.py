@@ -5,6 +5,7 @@
     WanVideoVAE.from_module(ref_vae)   <- borrow the fp32 parameters of a reference WanVideoVAE on the GPU
     .encode(videos, device, tiled=False, tile_size, tile_stride) -> Tensor[N,16,T',h,w]      vae:759-774
     .decode(hidden_states, device, tiled=False, tile_size, tile_stride) -> Tensor[N,3,T,H,W] vae:777-789
+    .decode(..., split=(ph, pw), group=None) / .decode_part(latent, split, part, out=None)   exact spatial split over ranks (not in the reference)
 
 The whole clip stays resident in HBM (no temporal chunking, no feature cache: see csrc/svi_vae.hip).  `tiled=True`
 is the reference's spatial tiling and linear-ramp blending (vae:621-744) in one C call (svi_vae_tiled_decode / _encode): tiles are read
@@ -14,7 +15,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-from typing import Dict, List, Sequence
+from typing import Dict, List, Optional, Sequence
 
 import torch
 
@@ -92,6 +93,22 @@ def device_vae_weights(seed: int, device) -> Dict[str, torch.Tensor]:
             t = (torch.rand(shape, generator=g, device=device) * 2 - 1) * 0.05
         out[name] = t.float().contiguous()
     return out
+
+
+def default_vae_split(world: int) -> tuple:
+    """The decode grid of a latency-mode group of `world` ranks: 2 -> 1 x 2, 4 -> 2 x 2, 8 -> 2 x 4, otherwise 1 x P along the width."""
+    return {2: (1, 2), 4: (2, 2), 8: (2, 4)}.get(int(world), (1, int(world)))
+
+
+def latency_group(loop):
+    """The process group whose ranks share every clip of a DenoiseLoop (its CFG pair, else its sequence-parallel group; the world when that is
+    None) — the ranks that would otherwise wait for one of them to decode.  None for a single-rank loop."""
+    import torch.distributed as dist
+    if getattr(loop, "cfg_pair", None) is not None:
+        return loop.cfg_pair.group if loop.cfg_pair.group is not None else dist.group.WORLD
+    if getattr(loop, "sequence_parallel", False):
+        return loop.sp_group if loop.sp_group is not None else dist.group.WORLD
+    return None
 
 
 class WanVideoVAE:
@@ -193,11 +210,86 @@ class WanVideoVAE:
             outs.append(hs.squeeze(0))
         return torch.stack(outs)
 
-    def decode(self, hidden_states, device=None, tiled=False, tile_size=(34, 34), tile_stride=(18, 16)):
+    # ---- exact spatial split for the multi-rank latency modes (svi_vae_split_plan / svi_vae_decode_part) --------------------------------
+    def decode_part(self, hidden_state: torch.Tensor, split, part: int, out: Optional[torch.Tensor] = None, _short_halo: int = 0) -> torch.Tensor:
+        """Part `part` (row-major) of a split = (parts_h, parts_w) decode of ONE latent [16,T,h,w] or [1,16,T,h,w] (always the whole latent: the
+        middle block attends over the frame).  out=None: a tight [3,T',oh,ow] tensor of the owned window.  out = a [3,T',H,W] tensor with
+        H >= oh, W >= ow: the full frame [3,T',8h,8w] receives the window at its place, any other size (an all-gather buffer) at its origin;
+        nothing outside the window is written.  `_short_halo` is for tests only: decode with the stage 0 halo that many latent pixels short."""
+        z = hidden_state.to(device="cuda", dtype=torch.float32)
+        z = (z[0] if z.dim() == 5 else z).contiguous()
+        c, t, h, w = z.shape
+        if c != 16:
+            raise ValueError("latents must have 16 channels")
+        ph, pw = int(split[0]), int(split[1])
+        plan = L.vae_split_plan(h, w, ph, pw, int(part))
+        h0, h1, w0, w1 = plan["owned"]
+        oh, ow, tv = 8 * (h1 - h0), 8 * (w1 - w0), 1 + 4 * (t - 1)
+        if out is None:
+            out = torch.empty((3, tv, oh, ow), dtype=torch.float32, device=z.device)
+        if not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.dim() == 4 and out.shape[0] == 3 and out.shape[1] == tv
+                and out.shape[2] >= oh and out.shape[3] >= ow):
+            raise ValueError(f"decode_part: out must be a contiguous CUDA fp32 [3, {tv}, >= {oh}, >= {ow}] tensor, got {tuple(out.shape)}")
+        ld_h, ld_w = out.shape[2], out.shape[3]
+        full = (ld_h, ld_w) == (8 * h, 8 * w)
+        dst = out.data_ptr() + 4 * ((8 * h0) * ld_w + 8 * w0) if full else out.data_ptr()
+        if _short_halo:
+            s0 = plan["padded"][0]
+            own = plan["owned"]
+            cut = [min(s0[0] + _short_halo, own[0]), max(s0[1] - _short_halo, own[1]), min(s0[2] + _short_halo, own[2]), max(s0[3] - _short_halo, own[3])]
+            flat = list(own) + list(plan["halo"]) + cut + [v for r in plan["padded"][1:] for v in r]
+            L.check(L.lib().svi_vae_decode_planned(self._h, L.ptr(z), dst, t, h, w, (C.c_int32 * 24)(*flat), ld_h, ld_w, L.current_stream()), "svi_vae_decode_planned")
+        else:
+            L.check(L.lib().svi_vae_decode_part(self._h, L.ptr(z), dst, t, h, w, ph, pw, int(part), ld_h, ld_w, L.current_stream()), "svi_vae_decode_part")
+        return out
+
+    def split_decode(self, hidden_state: torch.Tensor, split, group=None) -> torch.Tensor:
+        """[1,16,T,h,w] -> [1,3,T',8h,8w].  group=None: every part in this process, one after another, into one frame (the local schedule: tests and
+        timing).  With a process group of parts_h x parts_w ranks: this rank's part into a tight buffer, one all-gather, the frame assembled on
+        every rank."""
+        z = hidden_state.to(device="cuda", dtype=torch.float32).contiguous()
+        _, c, t, h, w = z.shape
+        ph, pw = int(split[0]), int(split[1])
+        n = ph * pw
+        if group is not None:                            # refuse a mismatch before any collective
+            import torch.distributed as dist
+            world = dist.get_world_size(group)
+            if world != n:
+                raise ValueError(f"VAE split {ph} x {pw} needs a group of {n} ranks, this one has {world}")
+        if n == 1:
+            return self.single_decode(z)
+        tv = 1 + 4 * (t - 1)
+        out = torch.empty((1, 3, tv, 8 * h, 8 * w), dtype=torch.float32, device=z.device)
+        if group is None:
+            for p in range(n):
+                self.decode_part(z, (ph, pw), p, out=out[0])
+            return out
+        import torch.distributed as dist
+        from .sequence_parallel import GroupTransport, _wait
+        owned = [L.vae_split_plan(h, w, ph, pw, p)["owned"] for p in range(n)]
+        mh, mw = 8 * max(o[1] - o[0] for o in owned), 8 * max(o[3] - o[2] for o in owned)
+        if (mh, mw) == (8 * h, 8 * w):                   # (cannot happen for n > 1; keeps a gather buffer from being taken for the full frame)
+            raise ValueError("VAE split: a part as large as the frame")
+        mine = torch.zeros((3, tv, mh, mw), dtype=torch.float32, device=z.device)   # parts are unequal when the grid does not divide: one size for the gather
+        self.decode_part(z, (ph, pw), dist.get_rank(group), out=mine)
+        parts = torch.empty((n,) + tuple(mine.shape), dtype=torch.float32, device=z.device)
+        _wait(GroupTransport(group).all_gather([parts], [mine]))
+        for p, (h0, h1, w0, w1) in enumerate(owned):
+            out[0, :, :, 8 * h0:8 * h1, 8 * w0:8 * w1] = parts[p, :, :, :8 * (h1 - h0), :8 * (w1 - w0)]
+        return out
+
+    def decode(self, hidden_states, device=None, tiled=False, tile_size=(34, 34), tile_stride=(18, 16), split=None, group=None):
+        """split = (parts_h, parts_w): the exact spatial split (see split_decode); group: the process group whose ranks each decode one part."""
+        if split is not None and tiled:
+            raise ValueError("VAE decode: tiled=True blends overlapping tiles, split=(ph, pw) is the exact rank split; ask for one of them")
+        if split is None and group is not None:
+            raise ValueError("VAE decode: a group needs split=(parts_h, parts_w)")
         outs: List[torch.Tensor] = []
         for hs in hidden_states:
             hs = hs.unsqueeze(0)
-            if tiled:
+            if split is not None:
+                video = self.split_decode(hs, split, group)
+            elif tiled:
                 video = self.tiled_decode(hs, device, tile_size, tile_stride)
             else:
                 video = self.single_decode(hs, device)

@@ -442,6 +442,31 @@ svi_status svi_vae_decode_part(svi_vae* h, const float* latents, float* video, i
 svi_status svi_vae_decode_planned(svi_vae* h, const float* latents, float* video, int32_t T, int32_t hh, int32_t ww, const int32_t* plan24,
                                   int32_t video_ld_h, int32_t video_ld_w, svi_stream stream);
 
+/* Exact spatial split of the encode, the decode split run the other way round: everything in front of the encoder's middle block is local, so a
+ * part runs conv1 and the four down stages on a crop of the video and writes its owned rectangle of the feature map entering middle.0; one
+ * all-gather assembles that map, and the middle block, the head and model.conv1 (svi_vae_encode_tail) run on the whole frame on every rank.
+ * svi_vae_encode_split_plan (host arithmetic, no device): part = i * parts_w + j of a parts_h x parts_w split of the hh x ww latent grid, cut as
+ *   svi_vae_split_plan cuts it.  There are five entry points: the video and the entries of stages 0-3, at 8, 8, 4, 2 and 1 pixels per latent
+ *   pixel.  out34 = {owned latent rectangle h0, h1, w0, w1 | reach (top/left, bottom/right) at the five entry points, derived from the encoder's
+ *   layer table | the rectangle (h0, h1, w0, w1) the part needs at the five entry points}: the owned rectangle scaled, grown by the reach, its
+ *   origin rounded down to a multiple of the entry point's factor (which keeps the phase of every stride-2 convolution behind it), clamped at the
+ *   image border (where the kernels' zero padding, the asymmetric right/bottom one included, is the real padding).  A 1 x 1 split reports no reach.
+ * svi_vae_encode_part: video f32 [3, T, H, W] (whole; the part's window is read in place) -> the part's owned window of the feature map,
+ *   channels-last f32 [T', h, w, C] (T' = 1 + (T - 1) / 4, C = the middle block's channels, 384).  `feat_out` (16-byte aligned) points at where the
+ *   window's first pixel goes; pixel (t, y, x) of the window is written at ((t ld_h + y) ld_w + x) C.  A full map: ld_h = H / 8, ld_w = W / 8 and
+ *   `feat_out` offset to the window; a tight buffer: the window's own size.  Nothing else is written.
+ * svi_vae_encode_planned: the same with the caller's plan (svi_vae_encode_split_plan's layout; the reach entries are not read).  The rectangles
+ *   are held to what keeps every window inside its tensor (and to even origins in front of the stride-2 convolutions), not to the reach: a plan
+ *   with a short halo encodes with errors next to the cuts.
+ * svi_vae_encode_tail: feat f32 [T', hh, ww, C] (tight) -> latents [16, T', hh, ww]: middle.0/1/2, head.0, head.2, model.conv1 and the latent
+ *   normalisation, the same code svi_vae_encode runs behind its down stages. */
+svi_status svi_vae_encode_split_plan(int32_t hh, int32_t ww, int32_t parts_h, int32_t parts_w, int32_t part, int32_t* out34);
+svi_status svi_vae_encode_part(svi_vae* h, const float* video, float* feat_out, int32_t T, int32_t H, int32_t W, int32_t parts_h, int32_t parts_w,
+                               int32_t part, int32_t ld_h, int32_t ld_w, svi_stream stream);
+svi_status svi_vae_encode_planned(svi_vae* h, const float* video, float* feat_out, int32_t T, int32_t H, int32_t W, const int32_t* plan34,
+                                  int32_t ld_h, int32_t ld_w, svi_stream stream);
+svi_status svi_vae_encode_tail(svi_vae* h, const float* feat, float* latents, int32_t Tl, int32_t hh, int32_t ww, svi_stream stream);
+
 /* ------------------------------------------------------------------ dance variant: pose embedder ------- */
 /* The `dwpose_embedding` of SVIDanceVideoPipeline (pipelines/svi_video_dance.py:255-269): seven fp32 Conv3d layers with SiLU between
  * them, 3 -> hidden (16) channels at full resolution down to dim channels at the DiT's token grid.  svi_pose_forward also does what

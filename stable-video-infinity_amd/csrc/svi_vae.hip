@@ -2243,31 +2243,16 @@ svi_status decode_part_graph(svi_vae* h, const float* latents, float* video, int
     return SVI_OK;
 }
 
-svi_status encode_graph(svi_vae* h, const float* video, float* latents, int T, int H, int W, hipStream_t st) {
+// The encoder's layers from the entry of middle.0 to the latents: middle block, head, model.conv1 and the latent output (or, for a tile of
+// svi_vae_tiled_encode, its blend).  One body for the whole encode and for svi_vae_encode_tail; consumes x.
+svi_status encode_tail_layers(svi_vae* h, Tens* x, float* latents, hipStream_t st) {
     const std::string e = "model.encoder.";
-    Tens v = alloc_t(h, T, H, W, 4);
-    NEED(v);
-    if (!h->dry) {
-        const long thw = (long)T * H * W;
-        if (h->win) hipLaunchKernelGGL(video_in_win_kernel, dim3((unsigned)((thw * 4 + 255) / 256)), dim3(256), 0, st, video, v.p, T, *h->win);
-        else hipLaunchKernelGGL(video_in_kernel, dim3((unsigned)((thw * 4 + 255) / 256)), dim3(256), 0, st, video, v.p, thw);
-        SVI_LAUNCH_CHECK();
-    }
-    Tens x;
-    SVI_TRY(conv_layer(h, e + "conv1", v, &x, st));
-    free_t(h, v);
-    const bool tdown[3] = {false, true, true};
-    int idx = 0;
-    for (int i = 0; i < 4; ++i) {
-        for (int r = 0; r < 2; ++r) SVI_TRY(res_block(h, e + "downsamples." + std::to_string(idx++) + ".", &x, st));
-        if (i != 3) SVI_TRY(downsample_block(h, e + "downsamples." + std::to_string(idx++) + ".", &x, tdown[i], st));
-    }
-    SVI_TRY(res_block(h, e + "middle.0.", &x, st));
-    SVI_TRY(attn_block(h, e + "middle.1.", &x, st));
-    SVI_TRY(res_block(h, e + "middle.2.", &x, st));
+    SVI_TRY(res_block(h, e + "middle.0.", x, st));
+    SVI_TRY(attn_block(h, e + "middle.1.", x, st));
+    SVI_TRY(res_block(h, e + "middle.2.", x, st));
     Tens n, hd, mu;
-    SVI_TRY(norm_act(h, e + "head.0.gamma", x, &n, 1, st, planes_scale_for(h, e + "head.2", e + "head.0.gamma", x)));
-    free_t(h, x);
+    SVI_TRY(norm_act(h, e + "head.0.gamma", *x, &n, 1, st, planes_scale_for(h, e + "head.2", e + "head.0.gamma", *x)));
+    free_t(h, *x);
     SVI_TRY(conv_layer(h, e + "head.2", n, &hd, st));
     free_t(h, n);
     SVI_TRY(conv_layer(h, "model.conv1", hd, &mu, st));
@@ -2281,6 +2266,198 @@ svi_status encode_graph(svi_vae* h, const float* video, float* latents, int T, i
     }
     free_t(h, mu);
     return SVI_OK;
+}
+
+// The encoder in front of the middle block, as encode_graph walks it: two residual blocks per stage, a downsample block behind stages 0-2.
+struct EncStage { std::string res[2], down; bool temporal; };
+static void encoder_stages(EncStage out[4]) {
+    const std::string e = "model.encoder.";
+    const bool tdown[3] = {false, true, true};
+    int idx = 0;
+    for (int i = 0; i < 4; ++i) {
+        for (int r = 0; r < 2; ++r) out[i].res[r] = e + "downsamples." + std::to_string(idx++) + ".";
+        out[i].down = i != 3 ? e + "downsamples." + std::to_string(idx++) + "." : std::string();
+        out[i].temporal = i != 3 && tdown[i];
+    }
+}
+
+svi_status encode_graph(svi_vae* h, const float* video, float* latents, int T, int H, int W, hipStream_t st) {
+    const std::string e = "model.encoder.";
+    Tens v = alloc_t(h, T, H, W, 4);
+    NEED(v);
+    if (!h->dry) {
+        const long thw = (long)T * H * W;
+        if (h->win) hipLaunchKernelGGL(video_in_win_kernel, dim3((unsigned)((thw * 4 + 255) / 256)), dim3(256), 0, st, video, v.p, T, *h->win);
+        else hipLaunchKernelGGL(video_in_kernel, dim3((unsigned)((thw * 4 + 255) / 256)), dim3(256), 0, st, video, v.p, thw);
+        SVI_LAUNCH_CHECK();
+    }
+    Tens x;
+    SVI_TRY(conv_layer(h, e + "conv1", v, &x, st));
+    free_t(h, v);
+    EncStage stg[4];
+    encoder_stages(stg);
+    for (int i = 0; i < 4; ++i) {
+        for (int r = 0; r < 2; ++r) SVI_TRY(res_block(h, stg[i].res[r], &x, st));
+        if (i != 3) SVI_TRY(downsample_block(h, stg[i].down, &x, stg[i].temporal, st));
+    }
+    return encode_tail_layers(h, &x, latents, st);
+}
+
+// ---- exact spatial split of the encode (svi_vae_encode_split_plan / svi_vae_encode_part / svi_vae_encode_tail) -----------------------
+// The decode split run the other way round: everything in FRONT of the encoder's middle block is local (3-tap convolutions, per-pixel
+// norms, 1x1 shortcuts, stride-2 resample convolutions), so a part runs conv1 and the four down stages on a crop of the video and writes
+// its owned rectangle of the feature map entering middle.0; the middle block, the head and model.conv1 then run on the assembled map.
+// The rectangle a part needs at an entry point is its owned rectangle, scaled, grown by what the layers between that point and middle.0
+// reach; the crop is trimmed to the next entry point's rectangle after every downsample block.
+struct EncSplitPlan {
+    int own[4];                      // owned latent rectangle {h0, h1, w0, w1}
+    int reach[5][2];                 // {top/left, bottom/right} at the entry points video, stage 0, 1, 2, 3, in pixels of that resolution
+    int rect[5][4];                  // rectangle needed at those entry points, in that resolution (video and stage 0: x 8; stage s: x 2^(3-s))
+};
+static inline int enc_factor(int entry) { return entry == 0 ? 8 : 8 >> (entry - 1); }      // resolution of an entry point relative to the latent grid
+
+// How far the layers between each entry point and the entry of middle.0 reach, from the architecture table, walked backwards: a residual
+// block adds the larger of its two convolutions in a row and its shortcut; a time_conv adds its spatial taps (none); a resample
+// convolution is ZeroPad2d(0, 1, 0, 1) + a k-tap stride-2 convolution, output o reads inputs 2o .. 2o + k - 1, so a need of n behind it
+// becomes 2n on the top/left and 2n + k - 2 on the bottom/right.
+static void encoder_reaches(int reach[5][2]) {
+    static const svi_vae* arch = [] { svi_vae* a = new svi_vae(); declare_architecture(a); return a; }();
+    auto taps = [&](const std::string& name) {
+        auto c = arch->convs.find(name);
+        return c == arch->convs.end() ? 1 : std::max(c->second.kh, c->second.kw);
+    };
+    EncStage stg[4];
+    encoder_stages(stg);
+    int tl = 0, br = 0;
+    for (int s = 3; s >= 0; --s) {
+        if (s != 3) {
+            const int kt = taps(stg[s].down + "time_conv") / 2, k = taps(stg[s].down + "resample.1");
+            tl += kt; br += kt;
+            tl = 2 * tl; br = 2 * br + k - 2;
+        }
+        for (int r = 1; r >= 0; --r) {
+            const int n = std::max(taps(stg[s].res[r] + "residual.2") / 2 + taps(stg[s].res[r] + "residual.6") / 2, taps(stg[s].res[r] + "shortcut") / 2);
+            tl += n; br += n;
+        }
+        reach[1 + s][0] = tl; reach[1 + s][1] = br;
+    }
+    const int n = taps("model.encoder.conv1") / 2;
+    reach[0][0] = tl + n; reach[0][1] = br + n;
+}
+
+static svi_status encode_split_plan(int hh, int ww, int parts_h, int parts_w, int part, EncSplitPlan* pl) {
+    SVI_REQUIRE(hh > 0 && ww > 0 && parts_h > 0 && parts_w > 0, "svi_vae_encode_split_plan: the grid and the split must be positive (got %d x %d in %d x %d parts)", hh, ww, parts_h, parts_w);
+    SVI_REQUIRE(hh <= (1 << 20) && ww <= (1 << 20), "svi_vae_encode_split_plan: latent grid %d x %d is too large", hh, ww);
+    SVI_REQUIRE(parts_h <= hh && parts_w <= ww, "svi_vae_encode_split_plan: %d x %d parts of a %d x %d latent grid would leave a part without a pixel", parts_h, parts_w, hh, ww);
+    SVI_REQUIRE(part >= 0 && part < parts_h * parts_w, "svi_vae_encode_split_plan: part %d is outside the %d x %d split", part, parts_h, parts_w);
+    const int i = part / parts_w, j = part % parts_w;
+    pl->own[0] = (int)((long)i * hh / parts_h); pl->own[1] = (int)((long)(i + 1) * hh / parts_h);
+    pl->own[2] = (int)((long)j * ww / parts_w); pl->own[3] = (int)((long)(j + 1) * ww / parts_w);
+    encoder_reaches(pl->reach);
+    for (int k = 0; k < 5; ++k) {
+        // the origin keeps the phase of every stride-2 convolution behind it: a multiple of the entry point's factor, the need rounded up
+        const int f = enc_factor(k), tl = pl->reach[k][0], br = pl->reach[k][1];
+        pl->rect[k][0] = std::max(pl->own[0] * f - tl, 0) / f * f; pl->rect[k][1] = std::min(pl->own[1] * f + br, hh * f);
+        pl->rect[k][2] = std::max(pl->own[2] * f - tl, 0) / f * f; pl->rect[k][3] = std::min(pl->own[3] * f + br, ww * f);
+    }
+    if (parts_h * parts_w == 1) for (int k = 0; k < 5; ++k) pl->reach[k][0] = pl->reach[k][1] = 0;
+    return SVI_OK;
+}
+
+// A caller's plan may be anything: hold it to what keeps every window inside the tensor it is cut from (not to the reach, which is the
+// planner's business).  An odd origin in front of a resample convolution has no place in the output grid and is refused too.
+static svi_status encode_split_plan_check(const EncSplitPlan& pl, int hh, int ww) {
+    SVI_REQUIRE(hh <= (1 << 20) && ww <= (1 << 20), "svi_vae_encode_planned: latent grid %d x %d is too large", hh, ww);
+    SVI_REQUIRE(0 <= pl.own[0] && pl.own[0] < pl.own[1] && pl.own[1] <= hh && 0 <= pl.own[2] && pl.own[2] < pl.own[3] && pl.own[3] <= ww,
+                "svi_vae_encode_planned: owned rectangle [%d, %d) x [%d, %d) is not inside the %d x %d latent grid", pl.own[0], pl.own[1], pl.own[2], pl.own[3], hh, ww);
+    for (int k = 0; k < 5; ++k) {
+        const int f = enc_factor(k);
+        const int* r = pl.rect[k];
+        SVI_REQUIRE(0 <= r[0] && r[0] <= pl.own[0] * f && pl.own[1] * f <= r[1] && r[1] <= hh * f && 0 <= r[2] && r[2] <= pl.own[2] * f && pl.own[3] * f <= r[3] && r[3] <= ww * f,
+                    "svi_vae_encode_planned: entry %d rectangle [%d, %d) x [%d, %d) does not lie between the owned rectangle and the image", k, r[0], r[1], r[2], r[3]);
+        if (k == 1) {
+            const int* v = pl.rect[0];
+            SVI_REQUIRE(v[0] <= r[0] && r[1] <= v[1] && v[2] <= r[2] && r[3] <= v[3], "svi_vae_encode_planned: the stage 0 rectangle is not inside the video rectangle");
+        }
+        if (k > 1) {             // a crop [q0, q1) with an even origin leaves the downsample block as [q0 / 2, q0 / 2 + (q1 - q0) / 2)
+            const int* q = pl.rect[k - 1];
+            SVI_REQUIRE(q[0] % 2 == 0 && q[2] % 2 == 0, "svi_vae_encode_planned: stage %d rectangle starts at an odd pixel (%d, %d) in front of a stride-2 convolution", k - 2, q[0], q[2]);
+            SVI_REQUIRE(q[0] / 2 <= r[0] && r[1] <= q[0] / 2 + (q[1] - q[0]) / 2 && q[2] / 2 <= r[2] && r[3] <= q[2] / 2 + (q[3] - q[2]) / 2,
+                        "svi_vae_encode_planned: stage %d rectangle is not inside the downsampled stage %d rectangle", k - 1, k - 2);
+        }
+    }
+    return SVI_OK;
+}
+
+// channels-last [T, H, W, C] window (y0, x0, oh, ow) -> out[t][y][x][c] at the caller's pitches (ld_h rows per frame, ld_w pixels per row),
+// four channels per thread; `out` is where the window's first pixel goes; every offset is 64-bit
+__global__ __launch_bounds__(256) void feat_out_part_kernel(const float4* __restrict__ in, float4* __restrict__ out, long n, int H, int W, int c4, int y0, int x0,
+                                                            int oh, int ow, long ld_h, long ld_w) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int c = (int)(i % c4);
+    long sp = i / c4;
+    const int x = (int)(sp % ow); sp /= ow;
+    const int y = (int)(sp % oh);
+    const long t = sp / oh;
+    out[((t * ld_h + y) * ld_w + x) * c4 + c] = in[((t * H + y0 + y) * W + x0 + x) * c4 + c];
+}
+
+svi_status encode_part_graph(svi_vae* h, const float* video, float* feat_out, int T, int H, int W, const EncSplitPlan& pl, long ld_h, long ld_w, hipStream_t st) {
+    const std::string e = "model.encoder.";
+    const int* vr = pl.rect[0];
+    Tens v = alloc_t(h, T, vr[1] - vr[0], vr[3] - vr[2], 4);
+    NEED(v);
+    if (!h->dry) {
+        TileWin w{};
+        w.Hf = H; w.Wf = W; w.h0 = vr[0]; w.w0 = vr[2]; w.th = v.H; w.tw = v.W;
+        SVI_REQUIRE(w.h0 >= 0 && w.w0 >= 0 && w.h0 + w.th <= H && w.w0 + w.tw <= W, "svi_vae_encode_part: the video window leaves the %d x %d video", H, W);
+        const long n = v.elems();
+        SVI_REQUIRE((n + 255) / 256 < (1L << 31), "svi_vae_encode_part: the video window is too large for one launch");
+        hipLaunchKernelGGL(video_in_win_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, video, v.p, T, w);
+        SVI_LAUNCH_CHECK();
+    }
+    Tens x;
+    SVI_TRY(conv_layer(h, e + "conv1", v, &x, st));
+    free_t(h, v);
+    {
+        const int* r = pl.rect[1];
+        SVI_TRY(crop_t(h, &x, r[0] - vr[0], r[2] - vr[2], r[1] - r[0], r[3] - r[2], st));
+    }
+    EncStage stg[4];
+    encoder_stages(stg);
+    for (int i = 0; i < 4; ++i) {
+        for (int r = 0; r < 2; ++r) SVI_TRY(res_block(h, stg[i].res[r], &x, st));
+        if (i != 3) {
+            SVI_TRY(downsample_block(h, stg[i].down, &x, stg[i].temporal, st));
+            const int* q = pl.rect[1 + i];           // x now covers [q0 / 2, q0 / 2 + (q1 - q0) / 2); trim it to what the stages behind still need
+            const int* r = pl.rect[2 + i];
+            SVI_TRY(crop_t(h, &x, r[0] - q[0] / 2, r[2] - q[2] / 2, r[1] - r[0], r[3] - r[2], st));
+        }
+    }
+    if (!h->dry) {
+        const int y0 = pl.own[0] - pl.rect[4][0], x0 = pl.own[2] - pl.rect[4][2], oh = pl.own[1] - pl.own[0], ow = pl.own[3] - pl.own[2];
+        SVI_REQUIRE(y0 >= 0 && x0 >= 0 && y0 + oh <= x.H && x0 + ow <= x.W, "svi_vae_encode_part: the owned window leaves the encoded crop");
+        SVI_REQUIRE(x.T == 1 + (T - 1) / 4 && x.C % 4 == 0 && x.plane_scale == 0.f, "svi_vae_encode_part: unexpected feature map [%d, %d, %d, %d]", x.T, x.H, x.W, x.C);
+        const long n = (long)x.T * oh * ow * (x.C / 4);
+        SVI_REQUIRE((n + 255) / 256 < (1L << 31), "svi_vae_encode_part: the owned window is too large for one launch");
+        SviProfScope _p(PROF_VAE_OTHER, st);
+        hipLaunchKernelGGL(feat_out_part_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, reinterpret_cast<const float4*>(x.p), reinterpret_cast<float4*>(feat_out), n,
+                           x.H, x.W, x.C / 4, y0, x0, oh, ow, ld_h, ld_w);
+        SVI_LAUNCH_CHECK();
+    }
+    free_t(h, x);
+    return SVI_OK;
+}
+
+// channels of the feature map entering middle.0, from the architecture table
+static int encoder_feat_channels(const svi_vae* h) { return h->convs.at("model.encoder.middle.0.residual.2").Cin; }
+
+svi_status encode_tail_graph(svi_vae* h, const float* feat, float* latents, int Tl, int hh, int ww, hipStream_t st) {
+    Tens x = alloc_t(h, Tl, hh, ww, encoder_feat_channels(h));
+    NEED(x);
+    if (!h->dry) SVI_CHECK_HIP(hipMemcpyAsync(x.p, feat, (size_t)x.elems() * 4, hipMemcpyDeviceToDevice, st));
+    return encode_tail_layers(h, &x, latents, st);
 }
 
 svi_status ensure_pool(svi_vae* h, long max_elems) {
@@ -2503,6 +2680,69 @@ extern "C" svi_status svi_vae_encode(svi_vae* h, const float* video, float* late
     SVI_TRY(ensure_pool(h, h->dry_max));
     h->slot_used.assign(h->nslots, 0);
     return encode_graph(h, video, latents, T, H, W, st);
+}
+
+// out34 = {owned h0, h1, w0, w1 | reach (top/left, bottom/right) at the video, stages 0-3 | rectangle (h0, h1, w0, w1) at the video, stages 0-3}.
+// Host arithmetic only.
+extern "C" svi_status svi_vae_encode_split_plan(int32_t hh, int32_t ww, int32_t parts_h, int32_t parts_w, int32_t part, int32_t* out34) {
+    SVI_REQUIRE(out34, "svi_vae_encode_split_plan: null argument");
+    EncSplitPlan pl{};
+    SVI_TRY(encode_split_plan(hh, ww, parts_h, parts_w, part, &pl));
+    for (int k = 0; k < 4; ++k) out34[k] = pl.own[k];
+    for (int k = 0; k < 5; ++k) { out34[4 + 2 * k] = pl.reach[k][0]; out34[5 + 2 * k] = pl.reach[k][1]; }
+    for (int k = 0; k < 5; ++k) for (int m = 0; m < 4; ++m) out34[14 + 4 * k + m] = pl.rect[k][m];
+    return SVI_OK;
+}
+
+static svi_status encode_with_plan(svi_vae* h, const float* video, float* feat_out, int T, int H, int W, const EncSplitPlan& pl, int32_t ld_h, int32_t ld_w, hipStream_t st) {
+    SVI_REQUIRE(ld_h >= pl.own[1] - pl.own[0] && ld_w >= pl.own[3] - pl.own[2], "svi_vae_encode_part: feature pitches %d rows x %d pixels are smaller than the owned window %d x %d",
+                ld_h, ld_w, pl.own[1] - pl.own[0], pl.own[3] - pl.own[2]);
+    SVI_REQUIRE(reinterpret_cast<uintptr_t>(feat_out) % 16 == 0, "svi_vae_encode_part: feat_out must be 16-byte aligned");
+    SVI_TRY(vae_prepare(h));
+    h->dry = true; h->dry_max = 0;
+    const svi_status dry = encode_part_graph(h, video, feat_out, T, H, W, pl, ld_h, ld_w, st);
+    h->dry = false;
+    SVI_TRY(dry);
+    SVI_TRY(ensure_pool(h, h->dry_max));
+    h->slot_used.assign(h->nslots, 0);
+    return encode_part_graph(h, video, feat_out, T, H, W, pl, ld_h, ld_w, st);
+}
+
+extern "C" svi_status svi_vae_encode_part(svi_vae* h, const float* video, float* feat_out, int32_t T, int32_t H, int32_t W, int32_t parts_h, int32_t parts_w,
+                                          int32_t part, int32_t ld_h, int32_t ld_w, svi_stream stream) {
+    SVI_REQUIRE(h && video && feat_out && T > 0 && H > 0 && W > 0, "svi_vae_encode_part: bad argument");
+    SVI_REQUIRE_DEVICE(h);
+    SVI_REQUIRE((T - 1) % 4 == 0 && H % 8 == 0 && W % 8 == 0, "svi_vae_encode_part: needs T = 1+4k frames and H, W multiples of 8 (got %d, %d, %d)", T, H, W);
+    EncSplitPlan pl{};
+    SVI_TRY(encode_split_plan(H / 8, W / 8, parts_h, parts_w, part, &pl));
+    return encode_with_plan(h, video, feat_out, T, H, W, pl, ld_h, ld_w, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" svi_status svi_vae_encode_planned(svi_vae* h, const float* video, float* feat_out, int32_t T, int32_t H, int32_t W, const int32_t* plan34,
+                                             int32_t ld_h, int32_t ld_w, svi_stream stream) {
+    SVI_REQUIRE(h && video && feat_out && plan34 && T > 0 && H > 0 && W > 0, "svi_vae_encode_planned: bad argument");
+    SVI_REQUIRE_DEVICE(h);
+    SVI_REQUIRE((T - 1) % 4 == 0 && H % 8 == 0 && W % 8 == 0, "svi_vae_encode_planned: needs T = 1+4k frames and H, W multiples of 8 (got %d, %d, %d)", T, H, W);
+    EncSplitPlan pl{};
+    for (int k = 0; k < 4; ++k) pl.own[k] = plan34[k];
+    for (int k = 0; k < 5; ++k) { pl.reach[k][0] = plan34[4 + 2 * k]; pl.reach[k][1] = plan34[5 + 2 * k]; }
+    for (int k = 0; k < 5; ++k) for (int m = 0; m < 4; ++m) pl.rect[k][m] = plan34[14 + 4 * k + m];
+    SVI_TRY(encode_split_plan_check(pl, H / 8, W / 8));
+    return encode_with_plan(h, video, feat_out, T, H, W, pl, ld_h, ld_w, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" svi_status svi_vae_encode_tail(svi_vae* h, const float* feat, float* latents, int32_t Tl, int32_t hh, int32_t ww, svi_stream stream) {
+    SVI_REQUIRE(h && feat && latents && Tl > 0 && hh > 0 && ww > 0, "svi_vae_encode_tail: bad argument");
+    SVI_REQUIRE_DEVICE(h);
+    SVI_TRY(vae_prepare(h));
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    h->dry = true; h->dry_max = 0;
+    const svi_status dry = encode_tail_graph(h, feat, latents, Tl, hh, ww, st);
+    h->dry = false;
+    SVI_TRY(dry);
+    SVI_TRY(ensure_pool(h, h->dry_max));
+    h->slot_used.assign(h->nslots, 0);
+    return encode_tail_graph(h, feat, latents, Tl, hh, ww, st);
 }
 
 // ---- tiled paths ------------------------------------------------------------------------------------------------------------

@@ -106,6 +106,10 @@ SYMBOLS = [
     ("svi_vae_split_plan", _i32, [_i32, _i32, _i32, _i32, _i32, C.POINTER(_i32)]),
     ("svi_vae_decode_part", _i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     ("svi_vae_decode_planned", _i32, [_vp, _vp, _vp, _i32, _i32, _i32, C.POINTER(_i32), _i32, _i32, _vp]),
+    ("svi_vae_encode_split_plan", _i32, [_i32, _i32, _i32, _i32, _i32, C.POINTER(_i32)]),
+    ("svi_vae_encode_part", _i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    ("svi_vae_encode_planned", _i32, [_vp, _vp, _vp, _i32, _i32, _i32, C.POINTER(_i32), _i32, _i32, _vp]),
+    ("svi_vae_encode_tail", _i32, [_vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     ("svi_pose_create", _i32, [_i32, _i32, C.POINTER(_vp)]),
     ("svi_pose_destroy", _i32, [_vp]),
     ("svi_pose_bind_weight", _i32, [_vp, C.c_char_p, _vp, _i32, C.POINTER(_i64), _i32]),
@@ -235,6 +239,18 @@ def vae_split_plan(hh: int, ww: int, parts_h: int, parts_w: int, part: int) -> d
     out = (_i32 * 24)()
     check(lib().svi_vae_split_plan(hh, ww, parts_h, parts_w, part, out), "svi_vae_split_plan")
     return {"owned": tuple(out[0:4]), "halo": tuple(out[4:8]), "padded": [tuple(out[8 + 4 * s:12 + 4 * s]) for s in range(4)]}
+
+
+VAE_ENCODE_ENTRIES = ("video", "stage0", "stage1", "stage2", "stage3")
+
+
+def vae_encode_split_plan(hh: int, ww: int, parts_h: int, parts_w: int, part: int) -> dict:
+    """One part of the exact spatial split of the VAE encode (see include/svi_hip.h): rectangles are (h0, h1, w0, w1); `owned` in latent pixels,
+    `rects[k]` what the part needs at entry point k of VAE_ENCODE_ENTRIES (8, 8, 4, 2, 1 pixels per latent pixel), `reach[k]` = (top/left,
+    bottom/right) in the same unit."""
+    out = (_i32 * 34)()
+    check(lib().svi_vae_encode_split_plan(hh, ww, parts_h, parts_w, part, out), "svi_vae_encode_split_plan")
+    return {"owned": tuple(out[0:4]), "reach": [tuple(out[4 + 2 * k:6 + 2 * k]) for k in range(5)], "rects": [tuple(out[14 + 4 * k:18 + 4 * k]) for k in range(5)]}
 
 
 def prof_select(tags=None) -> None:

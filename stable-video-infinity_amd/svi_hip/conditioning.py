@@ -59,16 +59,18 @@ def condition_video(first_frames: torch.Tensor, random_ref_frame: Optional[torch
 
 def image_condition(vae, first_frames: Union[torch.Tensor, Sequence[torch.Tensor]], random_ref_frame: Optional[torch.Tensor],
                     num_frames: int, ref_pad_cfg: bool = False, ref_pad_num: int = 0, out_dtype=torch.bfloat16,
-                    tiled: bool = False, tile_size=(34, 34), tile_stride=(18, 16), image_encoder=None):
+                    tiled: bool = False, tile_size=(34, 34), tile_stride=(18, 16), image_encoder=None, split=None, group=None):
     """y [1, 20, T', H/8, W/8] exactly as encode_images_adaptive returns it (mask ‖ VAE latent, cast to the DiT dtype).
     With `image_encoder` (svi_hip.WanImageEncoder): the call's full result {"clip_feature": ..., "y": ...} (:317, :355-364) — the CLIP
-    tokens of the FIRST motion frame, computed in fp32 and cast to the DiT dtype."""
+    tokens of the FIRST motion frame, computed in fp32 and cast to the DiT dtype.
+    split = (parts_h, parts_w) / group: the exact rank split of the VAE encode (WanVideoVAE.encode); off by default."""
     if not isinstance(first_frames, torch.Tensor):
         first_frames = torch.stack([f.reshape(3, *f.shape[-2:]) for f in first_frames])
     first_frames = first_frames.to(device="cuda", dtype=torch.float32)
     n, _, H, W = first_frames.shape
     video = condition_video(first_frames, random_ref_frame, num_frames, ref_pad_num)
-    lat = vae.encode([video], device="cuda", tiled=tiled, tile_size=tile_size, tile_stride=tile_stride)[0]
+    enc_split = dict(split=tuple(split), group=group) if split is not None else ({} if group is None else dict(group=group))
+    lat = vae.encode([video], device="cuda", tiled=tiled, tile_size=tile_size, tile_stride=tile_stride, **enc_split)[0]
     msk = condition_mask(num_frames, H, W, n, ref_pad_cfg, device=lat.device)
     y = torch.concat([msk, lat]).unsqueeze(0).to(out_dtype)
     if image_encoder is None:

@@ -699,7 +699,8 @@ def _assert_resident(pipe, hip: WanDiT, full: bool = False) -> None:
         hip.check_module_in_place(dit_module)
 
 
-def install(pipe, vae: bool = True, encoders: bool = True, sampler: bool = True, resident: bool = True, vae_split=None, vae_group=None):
+def install(pipe, vae: bool = True, encoders: bool = True, sampler: bool = True, resident: bool = True, vae_split=None, vae_group=None,
+            vae_encode_split=None):
     """Route `pipe`'s hot path (SVIVideoPipeline / WanVideoPipeline of the reference) through libsvi_hip.
 
     * `model_fn_wan_video` in the pipeline's defining module is replaced by the HIP-backed function
@@ -710,7 +711,8 @@ def install(pipe, vae: bool = True, encoders: bool = True, sampler: bool = True,
       around it: every line outside the loop is the reference's);
     * `pipe.vae.encode/decode` are rebound to the HIP VAE (same signatures), when `vae` is true; `vae_split` = (parts_h, parts_w) (+ `vae_group`, whose
       ranks each decode one part; a group alone takes default_vae_split's grid) makes every decode the exact spatial split of WanVideoVAE.decode —
-      off by default; call the pipeline with tiled=False then, the blended tiling and the split exclude each other;
+      off by default; call the pipeline with tiled=False then, the blended tiling and the split exclude each other; `vae_encode_split` (a grid, or
+      True for default_vae_split's grid over `vae_group`) does the same for every encode (WanVideoVAE.encode), independent of `vae_split`, off by default;
     * `pipe.dit` stays the reference nn.Module: weights are borrowed, so call `install` again (or
       `pipe._svi_hip_dit.rebind()`) after `load_lora_v2`, `.to()` or any offload that moves storage.
     * with `encoders`: the prompter's `text_encoder(ids, mask)` (prompters/wan_prompter.py:109) and `pipe.image_encoder.encode_image`
@@ -738,11 +740,12 @@ def install(pipe, vae: bool = True, encoders: bool = True, sampler: bool = True,
     hip = WanDiT.from_module(dit_module)
     _route_dit(pipe, hip, sampler=sampler)
     if vae and getattr(pipe, "vae", None) is not None:
-        from .vae import WanVideoVAE
+        from .vae import WanVideoVAE, _encode_split_setting
         hv = WanVideoVAE.from_module(pipe.vae)
         pipe._svi_hip_vae = hv
+        enc_split = _encode_split_setting(vae_encode_split, vae_group)
         pipe.vae.encode = types.MethodType(lambda self, videos, device=None, tiled=False, tile_size=(34, 34),
-                                           tile_stride=(18, 16): hv.encode(videos, device, tiled, tile_size, tile_stride), pipe.vae)
+                                           tile_stride=(18, 16): hv.encode(videos, device, tiled, tile_size, tile_stride, **enc_split), pipe.vae)
         pipe._svi_hip_vae_split = _vae_split_setting(vae_split, vae_group)
         pipe.vae.decode = types.MethodType(lambda self, hidden_states, device=None, tiled=False, tile_size=(34, 34),
                                            tile_stride=(18, 16): hv.decode(hidden_states, device, tiled, tile_size, tile_stride,

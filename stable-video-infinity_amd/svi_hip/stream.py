@@ -19,7 +19,7 @@ import torch
 from . import _lib as L
 from .conditioning import image_condition
 from .pipeline import DenoiseLoop, generate_noise
-from .vae import default_vae_split, latency_group
+from .vae import _encode_split_setting, default_vae_split, latency_group
 
 
 def video_to_u8(video: torch.Tensor) -> torch.Tensor:
@@ -44,16 +44,23 @@ class StreamLoop:
     def __init__(self, dit, vae, clip_encoder: Optional[Callable[[torch.Tensor], torch.Tensor]] = None, num_motion_frames: int = 1,
                  num_frames: int = 81, num_inference_steps: int = 50, cfg_scale: float = 5.0, sigma_shift: float = 5.0,
                  ref_pad_cfg: bool = False, ref_pad_num: int = 0, seed_times: int = 42, tiled: bool = False, tile_size=(30, 52),
-                 tile_stride=(15, 26), vae_split=None, vae_group=None, cfg_pair=None, sp_group=None, sequence_parallel: bool = False):
+                 tile_stride=(15, 26), vae_split=None, vae_group=None, cfg_pair=None, sp_group=None, sequence_parallel: bool = False,
+                 vae_encode_split=None):
         """tiled / tile_size / tile_stride: the VAE tiling arguments SVIVideoPipeline.__call__ passes to decode_video (svi_video.py:439-441, 515;
         test_svi.py passes args.tiled, default False).  The conditioning encode is never tiled, as in the reference (:350).
         vae_split = (parts_h, parts_w) / vae_group: the exact spatial split of every clip's decode (WanVideoVAE.decode): with a group each rank
         decodes one part, without one all parts run here, one after another.  Off by default.  cfg_pair / sequence_parallel (+ sp_group): the
-        latency modes of DenoiseLoop; the decode then uses that group's ranks too, on default_vae_split's grid unless vae_split names one."""
+        latency modes of DenoiseLoop; the decode then uses that group's ranks too, on default_vae_split's grid unless vae_split names one.
+        vae_encode_split: the same split for every clip's conditioning encode (WanVideoVAE.encode), independent of vae_split and off by default
+        (None / False), in the latency modes too.  (parts_h, parts_w): that grid, over vae_group (else the latency group) when there is one, all
+        parts here otherwise.  True: default_vae_split's grid over that group; without a group there is nothing to split over."""
         if num_motion_frames < 1:
             raise ValueError("an image-conditioned stream hands at least one motion frame from clip to clip (test_svi.py:472-476)")
+        enc_group = vae_group
         if cfg_pair is not None or sequence_parallel:
             self.loop = DenoiseLoop(dit, cfg_pair=cfg_pair, sp_group=sp_group, sequence_parallel=sequence_parallel)
+            if enc_group is None:
+                enc_group = latency_group(self.loop)
             if vae_group is None and (vae_split is None or tuple(vae_split) != (1, 1)):
                 vae_group = latency_group(self.loop)
         else:
@@ -64,6 +71,7 @@ class StreamLoop:
         if vae_split is not None and tiled:
             raise ValueError("StreamLoop: tiled=True blends overlapping tiles, vae_split is the exact rank split; ask for one of them")
         self.vae_split = dict(split=tuple(vae_split), group=vae_group) if vae_split is not None else {}
+        self.vae_encode_split = _encode_split_setting(vae_encode_split, enc_group)
         self.vae, self.clip_encoder = vae, clip_encoder
         self.num_motion_frames, self.num_frames = num_motion_frames, num_frames
         self.steps, self.cfg_scale, self.sigma_shift = num_inference_steps, cfg_scale, sigma_shift
@@ -99,7 +107,7 @@ class StreamLoop:
         from .parallel import clip_prompt_index, clip_seed
         for k in clips:
             first = u8_to_video(motion)                                          # preprocess_image of every motion frame
-            y = image_condition(self.vae, first, ref, self.num_frames, self.ref_pad_cfg, self.ref_pad_num)
+            y = image_condition(self.vae, first, ref, self.num_frames, self.ref_pad_cfg, self.ref_pad_num, **self.vae_encode_split)
             if self.clip_encoder is None:
                 cf = clip_feature
             elif hasattr(self.clip_encoder, "encode_image"):                      # svi_hip.WanImageEncoder: clip_context of svi_video.py:317, :355

@@ -6,6 +6,7 @@
     .encode(videos, device, tiled=False, tile_size, tile_stride) -> Tensor[N,16,T',h,w]      vae:759-774
     .decode(hidden_states, device, tiled=False, tile_size, tile_stride) -> Tensor[N,3,T,H,W] vae:777-789
     .decode(..., split=(ph, pw), group=None) / .decode_part(latent, split, part, out=None)   exact spatial split over ranks (not in the reference)
+    .encode(..., split=(ph, pw), group=None) / .encode_part(video, split, part, out=None) / .encode_tail(feat)   the same for the encode
 
 The whole clip stays resident in HBM (no temporal chunking, no feature cache: see csrc/svi_vae.hip).  `tiled=True`
 is the reference's spatial tiling and linear-ramp blending (vae:621-744) in one C call (svi_vae_tiled_decode / _encode): tiles are read
@@ -95,9 +96,27 @@ def device_vae_weights(seed: int, device) -> Dict[str, torch.Tensor]:
     return out
 
 
+def encoder_feature_channels() -> int:
+    """Channels of the feature map entering the encoder's middle block (what encode_part writes and encode_tail reads)."""
+    return vae_param_shapes()["model.encoder.middle.0.residual.2.weight"][1]
+
+
 def default_vae_split(world: int) -> tuple:
     """The decode grid of a latency-mode group of `world` ranks: 2 -> 1 x 2, 4 -> 2 x 2, 8 -> 2 x 4, otherwise 1 x P along the width."""
     return {2: (1, 2), 4: (2, 2), 8: (2, 4)}.get(int(world), (1, int(world)))
+
+
+def _encode_split_setting(vae_encode_split, group) -> dict:
+    """What the conditioning encode passes on to WanVideoVAE.encode: nothing (the default), or split (+ group)."""
+    if vae_encode_split is None or vae_encode_split is False:
+        return {}
+    if vae_encode_split is True:
+        if group is None:
+            raise ValueError("vae_encode_split=True takes its grid from a process group (vae_group or a latency mode); name a grid (parts_h, parts_w) to split locally")
+        import torch.distributed as dist
+        vae_encode_split = default_vae_split(dist.get_world_size(group))
+    split = (int(vae_encode_split[0]), int(vae_encode_split[1]))
+    return dict(split=split, group=None if split == (1, 1) else group)
 
 
 def latency_group(loop):
@@ -195,11 +214,18 @@ class WanVideoVAE:
         return out
 
     # ---- public surface: vae:759-789 ----------------------------------------------------------------------------------
-    def encode(self, videos: Sequence[torch.Tensor], device=None, tiled=False, tile_size=(34, 34), tile_stride=(18, 16)):
+    def encode(self, videos: Sequence[torch.Tensor], device=None, tiled=False, tile_size=(34, 34), tile_stride=(18, 16), split=None, group=None):
+        """split = (parts_h, parts_w): the exact spatial split (see split_encode); group: the process group whose ranks each encode one part."""
+        if split is not None and tiled:
+            raise ValueError("VAE encode: tiled=True blends overlapping tiles, split=(ph, pw) is the exact rank split; ask for one of them")
+        if split is None and group is not None:
+            raise ValueError("VAE encode: a group needs split=(parts_h, parts_w)")
         outs: List[torch.Tensor] = []
         for video in videos:
             video = video.unsqueeze(0)
-            if tiled:
+            if split is not None:
+                hs = self.split_encode(video, split, group)
+            elif tiled:
                 # as the reference (vae:765-767): the x8 is applied to the loop's own variables, so from the second video of a
                 # batch on the tiles are 8x larger again (one tile per video in practice); kept, it is observable behaviour
                 tile_size = (tile_size[0] * 8, tile_size[1] * 8)
@@ -295,3 +321,92 @@ class WanVideoVAE:
                 video = self.single_decode(hs, device)
             outs.append(video.squeeze(0))
         return torch.stack(outs)
+
+    # ---- the same for the encode (svi_vae_encode_split_plan / svi_vae_encode_part / svi_vae_encode_tail) --------------------------------
+    def encode_part(self, video: torch.Tensor, split, part: int, out: Optional[torch.Tensor] = None, _short_halo: int = 0) -> torch.Tensor:
+        """Part `part` (row-major) of a split = (parts_h, parts_w) encode of ONE video [3,T,H,W] or [1,3,T,H,W] (always the whole video: the part's
+        window is read in place): conv1 and the down stages on the crop -> the owned window of the feature map entering the encoder's middle
+        block, channels-last fp32.  out=None: a tight [T',oh,ow,C] tensor.  out = a [T',h,w,C] tensor with h >= oh, w >= ow: the full map
+        [T',H/8,W/8,C] receives the window at its place, any other size (an all-gather slot) at its origin; nothing outside the window is written.
+        `_short_halo` is for tests only: encode with only that many video pixels of halo (a multiple of 8; the later rectangles shrink with it)."""
+        v = video.to(device="cuda", dtype=torch.float32)
+        v = (v[0] if v.dim() == 5 else v).contiguous()
+        c, t, H, W = v.shape
+        if c != 3:
+            raise ValueError("video must have 3 channels")
+        if (t - 1) % 4 or H % 8 or W % 8:
+            raise ValueError(f"encode_part: needs T = 1+4k frames and H, W multiples of 8 (got {t}, {H}, {W})")
+        ph, pw = int(split[0]), int(split[1])
+        h, w = H // 8, W // 8
+        plan = L.vae_encode_split_plan(h, w, ph, pw, int(part))
+        h0, h1, w0, w1 = plan["owned"]
+        oh, ow, tl, ch = h1 - h0, w1 - w0, 1 + (t - 1) // 4, encoder_feature_channels()
+        if out is None:
+            out = torch.empty((tl, oh, ow, ch), dtype=torch.float32, device=v.device)
+        if not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.dim() == 4 and out.shape[0] == tl and out.shape[3] == ch
+                and out.shape[1] >= oh and out.shape[2] >= ow):
+            raise ValueError(f"encode_part: out must be a contiguous CUDA fp32 [{tl}, >= {oh}, >= {ow}, {ch}] tensor, got {tuple(out.shape)}")
+        ld_h, ld_w = out.shape[1], out.shape[2]
+        full = (ld_h, ld_w) == (h, w)
+        dst = out.data_ptr() + 4 * ch * (h0 * ld_w + w0) if full else out.data_ptr()
+        if _short_halo:
+            if _short_halo % 8:
+                raise ValueError("encode_part: _short_halo is in video pixels, a multiple of 8")
+            rects = []
+            for k, (a0, a1, b0, b1) in enumerate(plan["rects"]):
+                f = 8 if k == 0 else 8 >> (k - 1)
+                n = _short_halo * f // 8
+                rects += [max(a0, h0 * f - n), min(a1, h1 * f + n), max(b0, w0 * f - n), min(b1, w1 * f + n)]
+            flat = list(plan["owned"]) + [x for r in plan["reach"] for x in r] + rects
+            L.check(L.lib().svi_vae_encode_planned(self._h, L.ptr(v), dst, t, H, W, (C.c_int32 * 34)(*flat), ld_h, ld_w, L.current_stream()), "svi_vae_encode_planned")
+        else:
+            L.check(L.lib().svi_vae_encode_part(self._h, L.ptr(v), dst, t, H, W, ph, pw, int(part), ld_h, ld_w, L.current_stream()), "svi_vae_encode_part")
+        return out
+
+    def encode_tail(self, feat: torch.Tensor) -> torch.Tensor:
+        """The assembled feature map [T',h,w,C] (channels-last fp32, what the parts of encode_part tile) -> latents [16,T',h,w]: the encoder's middle
+        block, head and model.conv1 on the whole frame."""
+        f = feat.to(device="cuda", dtype=torch.float32).contiguous()
+        if f.dim() != 4 or f.shape[3] != encoder_feature_channels():
+            raise ValueError(f"encode_tail: feat must be [T', h, w, {encoder_feature_channels()}], got {tuple(f.shape)}")
+        tl, h, w, _ = f.shape
+        out = torch.empty((16, tl, h, w), dtype=torch.float32, device=f.device)
+        L.check(L.lib().svi_vae_encode_tail(self._h, L.ptr(f), L.ptr(out), tl, h, w, L.current_stream()), "svi_vae_encode_tail")
+        return out
+
+    def split_encode(self, video: torch.Tensor, split, group=None) -> torch.Tensor:
+        """[1,3,T,H,W] -> [1,16,T',H/8,W/8].  group=None: every part in this process, one after another, into one feature map, then the tail (the
+        local schedule: tests and timing).  With a process group of parts_h x parts_w ranks: this rank's part into its slot, one all-gather, the
+        map assembled and the tail run on every rank."""
+        v = video.to(device="cuda", dtype=torch.float32).contiguous()
+        _, c, t, H, W = v.shape
+        ph, pw = int(split[0]), int(split[1])
+        n = ph * pw
+        if group is not None:                            # refuse a mismatch before any collective
+            import torch.distributed as dist
+            world = dist.get_world_size(group)
+            if world != n:
+                raise ValueError(f"VAE split {ph} x {pw} needs a group of {n} ranks, this one has {world}")
+        if n == 1:
+            return self.single_encode(v)
+        if c != 3:
+            raise ValueError("video must have 3 channels")
+        h, w, tl, ch = H // 8, W // 8, 1 + (t - 1) // 4, encoder_feature_channels()
+        owned = [L.vae_encode_split_plan(h, w, ph, pw, p)["owned"] for p in range(n)]       # refuses a part without a pixel
+        feat = torch.empty((tl, h, w, ch), dtype=torch.float32, device=v.device)
+        if group is None:
+            for p in range(n):
+                self.encode_part(v, (ph, pw), p, out=feat)
+            return self.encode_tail(feat)[None]
+        import torch.distributed as dist
+        from .sequence_parallel import GroupTransport, _wait
+        mh, mw = max(o[1] - o[0] for o in owned), max(o[3] - o[2] for o in owned)
+        if (mh, mw) == (h, w):                           # (cannot happen for n > 1; keeps a gather slot from being taken for the full map)
+            raise ValueError("VAE split: a part as large as the frame")
+        mine = torch.zeros((tl, mh, mw, ch), dtype=torch.float32, device=v.device)          # parts are unequal when the grid does not divide: one size for the gather
+        self.encode_part(v, (ph, pw), dist.get_rank(group), out=mine)
+        parts = torch.empty((n,) + tuple(mine.shape), dtype=torch.float32, device=v.device)
+        _wait(GroupTransport(group).all_gather([parts], [mine]))
+        for p, (h0, h1, w0, w1) in enumerate(owned):
+            feat[:, h0:h1, w0:w1] = parts[p, :, :h1 - h0, :w1 - w0]
+        return self.encode_tail(feat)[None]

@@ -20,7 +20,7 @@
  *   - Activations are bf16 (row-major, innermost dim contiguous) unless stated; accumulation fp32.
  *   - Handles are not thread-safe; one handle per device, driven from one host thread at a time.  What the library owns
  *     outside the handles — the attention kernels' per-workgroup flag words, the scratch of the operator-level seams
- *     (svi_attention_fwd, svi_layernorm_modulate, svi_rmsnorm_rope), the per-kernel LDS attributes, the event profiler's
+ *     (svi_attention_fwd, svi_layernorm_modulate, svi_rmsnorm_rope, svi_rmsnorm_rope_qk), the per-kernel LDS attributes, the event profiler's
  *     records — is keyed by (device, stream) and guarded by one mutex: two handles on two streams, or two host threads
  *     driving two streams, do not share a buffer (work on ONE stream is ordered, which is what protects a buffer between
  *     consecutive calls).  A stream that is being captured must have seen each call once before the capture (buffers are
@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define SVI_HIP_ABI_VERSION 11
+#define SVI_HIP_ABI_VERSION 12
 
 typedef enum {
     SVI_OK = 0,
@@ -295,6 +295,18 @@ svi_status svi_layernorm_modulate(const void* x, void* out, int32_t rows, int32_
 svi_status svi_rmsnorm_rope(void* x, int32_t ld, int32_t rows, int32_t dim, const void* weight, float eps,
                             int32_t rope, int32_t num_heads, int32_t f, int32_t h, int32_t w,
                             svi_stream stream);
+
+/* ABI v12 — the q | k normalisation as the DiT block launches it before every self-attention, in place on x[rows, ld]: operand q at columns [0, dim) with
+ * gain weight_q and output scale out_scale_q; with weight_k != NULL a second operand at columns [dim, 2 dim) (ld >= 2 dim) with weight_k / out_scale_k in
+ * the same launch.  The output scale multiplies the result before its single final rounding (the DiT folds softmax_scale * log2(e) into q there).
+ * rope: 0 none (f, h, w, row0, period ignored); 1 rotation pairs looked up in the three axis tables; 2 read from a per-token table gathered from them
+ * first — the form the DiT runs, and at dim 1536 / 5120 the four-rows-per-wave kernel.  Row i is token row0 + i of the (f, h, w) grid (a sequence-parallel
+ * shard starts mid-grid), or with period > 0 token row0 + i % period (samples of `period` rows stacked one under the other: the CFG pair).  Refused:
+ * dim > 8192, dim or ld not a multiple of 8, RoPE with dim % 128 != 0, a grid that does not hold [row0, row0 + rows) (with period: [row0, row0 + period),
+ * and rows must be a multiple of period), weight_k with ld < 2 dim.  The sequence-parallel send layout and the e4m3 output form are not reachable here. */
+svi_status svi_rmsnorm_rope_qk(void* x, int32_t ld, int32_t rows, int32_t dim, const void* weight_q, const void* weight_k,
+                               float eps, float out_scale_q, float out_scale_k, int32_t rope,
+                               int32_t f, int32_t h, int32_t w, int32_t row0, int32_t period, svi_stream stream);
 
 /* C[M,N] = epilogue(A[M,K] · W[N,K]^T)  — nn.Linear with the weight in its native [out,in] layout.
  * bias bf16 [N] (or [M] when bias_along_m, used to emit V^T); gate f32 [N] or NULL; res bf16 [M,ldres]

@@ -402,18 +402,15 @@ extern "C" svi_status svi_layernorm_modulate(const void* x, void* out, int32_t r
                              reinterpret_cast<const bf16*>(w), reinterpret_cast<const bf16*>(b), fs, fc, st);
 }
 
-extern "C" svi_status svi_rmsnorm_rope(void* x, int32_t ld, int32_t rows, int32_t dim, const void* weight, float eps,
-                                       int32_t rope, int32_t num_heads, int32_t f, int32_t h, int32_t w, svi_stream stream) {
-    SVI_REQUIRE(x && weight, "svi_rmsnorm_rope: null argument");
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (!rope)
-        return svi_launch_rmsnorm_rope(reinterpret_cast<bf16*>(x), ld, rows, dim, reinterpret_cast<const bf16*>(weight), eps, nullptr, 1.0f, st);
-    SVI_REQUIRE(num_heads > 0 && dim == num_heads * 128, "rope needs head_dim 128");
-    SVI_REQUIRE(f > 0 && h > 0 && w > 0 && f * h * w == rows, "rope grid %dx%dx%d != rows %d", f, h, w, rows);
-    // table built on the host in fp64 exactly as precompute_freqs_cis_3d does (dit:161-175)
+// The operator seams' RoPE tables for an (f, h, w) grid, in the stream's small scratch: the three axis tables built on the host in fp64 exactly as
+// precompute_freqs_cis_3d does (dit:161-175) and, with per_token, every token's 64 pairs gathered from them behind (SviRope::tab_tok, the DiT's own kernel).
+static svi_status seam_rope_tables(int f, int h, int w, bool per_token, hipStream_t st, SviRope* r) {
     const int dh = 128, d_hw = dh / 3, d_f = dh - 2 * d_hw;
     const int npf = d_f / 2, nph = d_hw / 2, npw = d_hw / 2;
     const size_t cnt = (size_t)f * npf + (size_t)h * nph + (size_t)w * npw;
+    const size_t n_axis = (cnt + 1) & ~(size_t)1;            // the per-token table starts 16-byte aligned
+    const size_t tokens = per_token ? (size_t)f * h * w : 0;
+    SVI_REQUIRE(tokens * 64 < ((size_t)1 << 31), "rope: grid %dx%dx%d too large", f, h, w);
     float2* host = (float2*)malloc(cnt * sizeof(float2));
     if (!host) { svi_set_error("out of host memory"); return SVI_ERR_OOM; }
     size_t o = 0;
@@ -425,7 +422,7 @@ extern "C" svi_status svi_rmsnorm_rope(void* x, int32_t ld, int32_t rows, int32_
                 host[o++] = make_float2((float)cos(ang), (float)sin(ang));
             }
     char* scr = nullptr;
-    svi_status s = scratch_reserve(cnt * sizeof(float2), st, &scr, SVI_BUF_SEAM_SMALL);
+    svi_status s = scratch_reserve((n_axis + tokens * 64) * sizeof(float2), st, &scr, SVI_BUF_SEAM_SMALL);
     if (s != SVI_OK) { free(host); return s; }
     // the scratch may still be read by work enqueued earlier (a previous call's table): drain the stream before rewriting it,
     // and the device after, since `st` need not be ordered after the null stream the copy runs on (operator seam, not the hot path)
@@ -434,12 +431,47 @@ extern "C" svi_status svi_rmsnorm_rope(void* x, int32_t ld, int32_t rows, int32_
     if (e == hipSuccess) e = hipDeviceSynchronize();
     free(host);
     if (e != hipSuccess) { svi_set_error("hipMemcpy(rope table) failed: %s", hipGetErrorString(e)); return SVI_ERR_HIP; }
+    *r = SviRope{};
+    r->tab_f = reinterpret_cast<const float2*>(scr);
+    r->tab_h = r->tab_f + (size_t)f * npf;
+    r->tab_w = r->tab_h + (size_t)h * nph;
+    r->npf = npf; r->nph = nph; r->npw = npw; r->f = f; r->h = h; r->w = w;
+    if (per_token) {
+        float2* tok = reinterpret_cast<float2*>(scr) + n_axis;
+        SVI_TRY(svi_launch_rope_token_table(*r, tok, (int)tokens, st));
+        r->tab_tok = tok;
+    }
+    return SVI_OK;
+}
+
+extern "C" svi_status svi_rmsnorm_rope(void* x, int32_t ld, int32_t rows, int32_t dim, const void* weight, float eps,
+                                       int32_t rope, int32_t num_heads, int32_t f, int32_t h, int32_t w, svi_stream stream) {
+    SVI_REQUIRE(x && weight, "svi_rmsnorm_rope: null argument");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (!rope)
+        return svi_launch_rmsnorm_rope(reinterpret_cast<bf16*>(x), ld, rows, dim, reinterpret_cast<const bf16*>(weight), eps, nullptr, 1.0f, st);
+    SVI_REQUIRE(num_heads > 0 && dim == num_heads * 128, "rope needs head_dim 128");
+    SVI_REQUIRE(f > 0 && h > 0 && w > 0 && f * h * w == rows, "rope grid %dx%dx%d != rows %d", f, h, w, rows);
     SviRope r{};
-    r.tab_f = reinterpret_cast<const float2*>(scr);
-    r.tab_h = r.tab_f + (size_t)f * npf;
-    r.tab_w = r.tab_h + (size_t)h * nph;
-    r.npf = npf; r.nph = nph; r.npw = npw; r.f = f; r.h = h; r.w = w;
+    SVI_TRY(seam_rope_tables(f, h, w, false, st, &r));
     return svi_launch_rmsnorm_rope(reinterpret_cast<bf16*>(x), ld, rows, dim, reinterpret_cast<const bf16*>(weight), eps, &r, 1.0f, st);
+}
+
+// The DiT's q | k launch (svi_dit.hip: svi_launch_rmsnorm_rope2 on the QK buffer) as an operator seam: what the launcher accepts and refuses is its own.
+extern "C" svi_status svi_rmsnorm_rope_qk(void* x, int32_t ld, int32_t rows, int32_t dim, const void* weight_q, const void* weight_k, float eps,
+                                          float out_scale_q, float out_scale_k, int32_t rope, int32_t f, int32_t h, int32_t w, int32_t row0,
+                                          int32_t period, svi_stream stream) {
+    SVI_REQUIRE(x && weight_q, "svi_rmsnorm_rope_qk: null argument");
+    SVI_REQUIRE(rope >= 0 && rope <= 2, "svi_rmsnorm_rope_qk: rope %d (0: none, 1: axis tables, 2: per-token table)", rope);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    SviRope r{};
+    if (rope) {
+        SVI_REQUIRE(f > 0 && h > 0 && w > 0, "svi_rmsnorm_rope_qk: rope grid %dx%dx%d", f, h, w);
+        SVI_TRY(seam_rope_tables(f, h, w, rope == 2, st, &r));
+        r.row0 = row0; r.period = period;
+    }
+    return svi_launch_rmsnorm_rope2(reinterpret_cast<bf16*>(x), ld, rows, dim, reinterpret_cast<const bf16*>(weight_q), reinterpret_cast<const bf16*>(weight_k), eps,
+                                    rope ? &r : nullptr, out_scale_q, out_scale_k, st);
 }
 
 extern "C" svi_status svi_gemm_bf16(const void* A, int32_t lda, const void* W, int32_t ldw, void* C, int32_t ldc, int32_t M,

@@ -289,6 +289,8 @@ struct SviRope {                // device tables of (cos,sin) pairs, fp32
                                 // (the stacked CFG pair: period = L on one rank, = the shard's row count on a sequence-parallel rank)
     const float2* tab_tok;      // optional: [f*h*w][64] — every token's 64 pairs gathered from the axis tables (16-byte aligned); the DiT builds it once per grid
 };
+// out[tok][64] = token tok's pairs gathered from r's three axis tables, tok in [0, tokens): what SviRope::tab_tok points at (svi_dit.hip; `out` 16-byte aligned)
+svi_status svi_launch_rope_token_table(const SviRope& r, float2* out, int tokens, hipStream_t st);
 // Sequence-parallel send layout (svi_hip/sequence_parallel.py): instead of in place, operand p of the q | k launch is stored as
 // out[p][g][j][row][cg] — destination rank j = col / Dp owns head-channel block [j*Dp, (j+1)*Dp), inside it head group g = (col % Dp) / Dg,
 // cg = col % Dg — so that every (operand, head group)'s all-to-all input is one contiguous [P][rows * Dg] tensor.

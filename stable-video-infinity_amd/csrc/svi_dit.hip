@@ -477,6 +477,13 @@ __global__ void rope_token_table_kernel(SviRope r, float2* __restrict__ out, int
     else cs = r.tab_w[pw * r.npw + (pi - r.npf - r.nph)];
     out[i] = cs;
 }
+svi_status svi_launch_rope_token_table(const SviRope& r, float2* out, int tokens, hipStream_t st) {
+    SVI_REQUIRE(r.tab_f && r.tab_h && r.tab_w && out && r.h > 0 && r.w > 0 && tokens >= 0 && (size_t)tokens * 64 < ((size_t)1 << 31), "rope: bad per-token table request (%d tokens)", tokens);
+    if (tokens == 0) return SVI_OK;
+    hipLaunchKernelGGL(rope_token_table_kernel, dim3((unsigned)(((size_t)tokens * 64 + 255) / 256)), dim3(256), 0, st, r, out, tokens);
+    SVI_LAUNCH_CHECK();
+    return SVI_OK;
+}
 
 // precompute_freqs_cis_3d (models/wan_video_dit.py:161-175): fp64 angles, stored as fp32 (cos, sin)
 static svi_status ensure_rope(svi_dit* h, int f, int hh, int ww) {
@@ -507,8 +514,7 @@ static svi_status ensure_rope(svi_dit* h, int f, int hh, int ww) {
     h->rope.npf = npf; h->rope.nph = nph; h->rope.npw = npw;
     h->rope.f = f; h->rope.h = hh; h->rope.w = ww;
     h->rope.tab_tok = nullptr;
-    hipLaunchKernelGGL(rope_token_table_kernel, dim3((unsigned)((tokens * 64 + 255) / 256)), dim3(256), 0, 0, h->rope, h->rope_dev + n_axis, (int)tokens);
-    SVI_LAUNCH_CHECK();
+    SVI_TRY(svi_launch_rope_token_table(h->rope, h->rope_dev + n_axis, (int)tokens, 0));
     SVI_CHECK_HIP(hipDeviceSynchronize());
     h->rope.tab_tok = h->rope_dev + n_axis;
     return SVI_OK;

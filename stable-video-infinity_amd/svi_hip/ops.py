@@ -81,6 +81,23 @@ def rmsnorm_rope_(x: torch.Tensor, weight: torch.Tensor, eps: float = 1e-6, grid
     return x
 
 
+def rmsnorm_rope_qk_(x: torch.Tensor, rows: int, dim: int, weight_q: torch.Tensor, weight_k: Optional[torch.Tensor] = None, eps: float = 1e-6,
+                     out_scale_q: float = 1.0, out_scale_k: float = 1.0, rope: int = 0, grid=(0, 0, 0), row0: int = 0, period: int = 0,
+                     ld: Optional[int] = None) -> int:
+    """The DiT's q | k launch (svi_rmsnorm_rope_qk, include/svi_hip.h), in place on the first `rows` rows of x [>= rows, ld]: RMSNorm (+ RoPE) of the
+    operand at columns [0, dim) and, with weight_k, of the one at [dim, 2 dim).  Returns the library's status as it is — 0, or what the launcher
+    refused (svi_hip._lib.last_error() has the text); nothing is checked here beyond what keeps the call inside x."""
+    _chk(x, "x"); _chk(weight_q, "weight_q")
+    if weight_k is not None:
+        _chk(weight_k, "weight_k")
+    ld = x.shape[-1] if ld is None else ld
+    if x.dim() != 2 or ld != x.shape[-1] or not 0 <= rows <= x.shape[0]:
+        raise ValueError(f"x {tuple(x.shape)} does not hold {rows} rows of ld {ld}")
+    f, h, w = grid
+    return L.lib().svi_rmsnorm_rope_qk(L.ptr(x), ld, rows, dim, L.ptr(weight_q), L.ptr(weight_k), eps, out_scale_q, out_scale_k, rope, f, h, w,
+                                       row0, period, L.current_stream())
+
+
 def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, epilogue: int = L.EPI_BIAS,
            gate: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
            transpose_out: bool = False) -> torch.Tensor:

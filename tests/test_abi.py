@@ -30,12 +30,13 @@ def test_ctypes_table_matches_header():
     assert sorted(n for n, _, _ in L.SYMBOLS) == declared_symbols()
 
 
-def test_abi_version_is_v11_in_header_and_library():
-    """v11 added the VAE convolution planners (svi_vae_conv_plan, svi_vae_tile_order); the header's define and the built library agree."""
+def test_abi_version_is_v12_in_header_and_library():
+    """v12 added the DiT's q | k RMSNorm + RoPE launch as an operator seam (svi_rmsnorm_rope_qk), v11 the VAE convolution planners
+    (svi_vae_conv_plan, svi_vae_tile_order); the header's define and the built library agree."""
     m = re.search(r"#define\s+SVI_HIP_ABI_VERSION\s+(\d+)", open(HEADER).read())
-    assert m and int(m.group(1)) == 11
-    assert L.lib().svi_abi_version() == 11
-    assert {"svi_vae_conv_plan", "svi_vae_tile_order"} <= set(declared_symbols())
+    assert m and int(m.group(1)) == 12
+    assert L.lib().svi_abi_version() == 12
+    assert {"svi_vae_conv_plan", "svi_vae_tile_order", "svi_rmsnorm_rope_qk"} <= set(declared_symbols())
 
 
 def test_dit_handle_lifecycle_and_errors():

@@ -153,6 +153,20 @@ svi_status svi_dit_forward_cfg_pair(svi_dit* h, const void* x, const float* time
                                     const void* context_uncond, const void* clip_feature, const void* y,
                                     const void* add_condition, void* out_cond, void* out_uncond, int32_t B, int32_t T,
                                     int32_t H, int32_t W, int32_t Lc, svi_stream stream);
+/* The CFG pair with TeaCache: svi_dit_forward_cfg_pair plus svi_dit_forward_tea's modes, for both branches in one call (additive in v12).
+ *   tea_mode 0: svi_dit_forward_cfg_pair, the residual arguments are ignored.
+ *   tea_mode 1 (store): the pair forward, prefix shared as above, which also leaves residual_k bf16 [B, L, dim] = bf16(x_after_blocks_k - x_before_blocks)
+ *     for k = cond, uncond.  x_before_blocks does not depend on the prompt: it is snapshotted once.
+ *   tea_mode 2 (skip): timestep embedding and patch embedding once; one row kernel reads a row of x and the matching rows of both residuals, forms
+ *     bf16(x + residual_k) — the rounding point of svi_dit_forward_tea's add — and writes the head's LayerNorm + modulate rows of both branches; the head
+ *     projection runs once over the 2 L stacked rows (per branch where the stacked workspace is not in use), unpatchify per branch.  The contexts are not read.
+ * Modes 1 and 2 need both residual buffers, distinct and 16-byte aligned; refusals otherwise as svi_dit_forward_cfg_pair (audio armed: SVI_ERR_UNSUPPORTED).
+ * Per (sample, branch) the outputs and residuals are bit-identical to two svi_dit_forward_tea calls with the respective context and residual. */
+svi_status svi_dit_forward_cfg_pair_tea(svi_dit* h, const void* x, const float* timestep, const void* context_cond,
+                                        const void* context_uncond, const void* clip_feature, const void* y,
+                                        const void* add_condition, void* out_cond, void* out_uncond, int32_t B, int32_t T,
+                                        int32_t H, int32_t W, int32_t Lc, int32_t tea_mode, void* residual_cond, void* residual_uncond,
+                                        svi_stream stream);
 
 /* Hoists what depends only on the prompt out of the step loop (SURVEY §8 a2 / f N2): with the cache enabled
  * svi_dit_forward projects a context (text_embedding / img_emb, pipelines/svi_video.py:94-99) and computes every block's

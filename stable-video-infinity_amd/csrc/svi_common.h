@@ -321,6 +321,9 @@ svi_status svi_launch_cfg3_step(bf16* lat, const bf16* cond, const bf16* uncond,
 svi_status svi_launch_video_to_u8(const float* video, unsigned char* out, long thw, hipStream_t st);
 svi_status svi_launch_u8_to_video(const unsigned char* frames, float* out, int n, long hw, hipStream_t st);
 svi_status svi_launch_sub_bf16(bf16* out, const bf16* a, const bf16* b, int64_t n, hipStream_t st);
+// out_k = modulate(LayerNorm(bf16(x + res_k))) for one or two residuals over the same rows of x (the TeaCache skip step of a CFG pair); res_b / out_b may be null
+svi_status svi_launch_add_ln_mod_pair(const bf16* x, const bf16* res_a, const bf16* res_b, bf16* out_a, bf16* out_b, int rows, int dim, float eps,
+                                      const float* shift, const float* scale1p, hipStream_t st);
 svi_status svi_launch_fp8_e4m3_to_bf16(const unsigned char* in, bf16* out, int64_t n, hipStream_t st);
 // fp32 C[M,N] = A[M,K] W[N,K]^T + bias[N] (+ res[M,N]) on the exact-fp32 MFMA kernel of the VAE (csrc/svi_vae.hip)
 svi_status svi_launch_gemm_f32(const float* A, int lda, const float* W, int ldw, const float* bias, float* C, int ldc, int M, int N, int K,

@@ -963,13 +963,18 @@ static CtxKV kv_of(svi_dit* h, const CtxUse& u, int l) {
 
 // head (dit:401-404): LN + modulation + Linear(dim -> out_dim * patch volume) on the rows in X -> HO [L, ho_ld]
 static int head_ld(const svi_dit_config& c) { return (c.out_dim * c.patch_t * c.patch_h * c.patch_w + 7) / 8 * 8; }
+// the head's Linear on the normed + modulated rows in Hb
+static svi_status stage_head_project(svi_dit* h, bf16* HO, int L, hipStream_t st, int nb = 1) {
+    const svi_dit_config& c = h->cfg;
+    const int ho = c.out_dim * c.patch_t * c.patch_h * c.patch_w;
+    return linear(h->ws.Hb, c.dim, h->head, HO, head_ld(c), L, ho, c.dim, SVI_EPI_BIAS, st, nullptr, nullptr, 0, nb);
+}
 static svi_status stage_head_rows(svi_dit* h, bf16* HO, int L, hipStream_t st, int nb = 1) {
     const svi_dit_config& c = h->cfg;
     Workspace& w = h->ws;
     const int D = c.dim;
-    const int ho = c.out_dim * c.patch_t * c.patch_h * c.patch_w;
     SVI_TRY(svi_launch_ln_mod(w.X, D, w.Hb, D, L, D, c.eps, nullptr, nullptr, w.headf, w.headf + D, st));
-    return linear(w.Hb, D, h->head, HO, head_ld(c), L, ho, D, SVI_EPI_BIAS, st, nullptr, nullptr, 0, nb);
+    return stage_head_project(h, HO, L, st, nb);
 }
 // unpatchify (dit:479-484) of all L = f*h*w head rows
 static svi_status stage_unpatchify(svi_dit* h, const bf16* HO, bf16* out, int T, int H, int W, hipStream_t st) {
@@ -1033,7 +1038,8 @@ static svi_status forward_one(svi_dit* h, const bf16* x, const float* timestep, 
 #define SVI_PAIR_STACK_MAX (1 << 20)       // tokens (A/B builds: -DSVI_PAIR_STACK_MAX=8192 is the round-1..4 behaviour: short sequences only)
 #endif
 static svi_status forward_pair(svi_dit* h, const bf16* x, const float* timestep, const bf16* ctx_a, const bf16* ctx_b, const bf16* clip,
-                               const bf16* y, const bf16* addc, bf16* out_a, bf16* out_b, int T, int H, int W, int Lc, hipStream_t st) {
+                               const bf16* y, const bf16* addc, bf16* out_a, bf16* out_b, int T, int H, int W, int Lc, hipStream_t st,
+                               int tea_mode = 0, bf16* res_a = nullptr, bf16* res_b = nullptr) {
     const svi_dit_config& c = h->cfg;
     const int D = c.dim;
     const int f = T / c.patch_t, hh = H / c.patch_h, ww = W / c.patch_w;
@@ -1056,9 +1062,32 @@ static svi_status forward_pair(svi_dit* h, const bf16* x, const float* timestep,
     Workspace& w = h->ws;
     SVI_TRY(stage_time(h, timestep, st));
     SVI_TRY(stage_embed(h, x, y, addc, T, H, W, L, st));
-    SVI_TRY(run_block_self(h, 0, w.X, w.modf, L, st));
     const bf16* ctxs[2] = {ctx_a, ctx_b};
     bf16* outs[2] = {out_a, out_b};
+    bf16* ress[2] = {res_a, res_b};
+    const size_t xbytes = (size_t)L * D * 2;
+    if (tea_mode == 2) {
+        // TeaCache skip (svi_video.py:68-70): no blocks, no prompt.  X (patch embedding, the same rows for both branches) is read once per row and left as it
+        // is; per branch bf16(X + residual) goes straight into the head's norm (svi_launch_add_ln_mod_pair).  The workspace keeps the layout the store mode
+        // chose for these sizes (same `stacked` decision), so alternating the modes moves no pointer a captured graph of either holds.
+        if (stacked) {
+            SVI_TRY(svi_launch_add_ln_mod_pair(w.X, res_a, res_b, w.Hb, w.Hb + (size_t)L * D, L, D, c.eps, w.headf, w.headf + D, st));
+            SVI_TRY(stage_head_project(h, w.HO, 2 * L, st, 2));
+            for (int k = 0; k < 2; ++k) SVI_TRY(stage_unpatchify(h, w.HO + (size_t)k * L * head_ld(c), outs[k], T, H, W, st));
+            return SVI_OK;
+        }
+        for (int k = 0; k < 2; ++k) {                // Hb / HO hold L rows: the head per branch
+            SVI_TRY(svi_launch_add_ln_mod_pair(w.X, ress[k], nullptr, w.Hb, nullptr, L, D, c.eps, w.headf, w.headf + D, st));
+            SVI_TRY(stage_head_project(h, w.HO, L, st));
+            SVI_TRY(stage_unpatchify(h, w.HO, outs[k], T, H, W, st));
+        }
+        return SVI_OK;
+    }
+    // TeaCache store (svi_video.py:64-66): x_before_blocks does not depend on the prompt — ONE snapshot serves both residuals.  Stacked: X2 is free (the
+    // second branch lives in X's lower half).  Unstacked: X2 holds the snapshot behind block 0's self-attention until the second branch restores it, so
+    // x_before_blocks waits in the second branch's residual buffer and moves to X2 once that is free.
+    if (tea_mode == 1) SVI_CHECK_HIP(hipMemcpyAsync(stacked ? w.X2 : res_b, w.X, xbytes, hipMemcpyDeviceToDevice, st));
+    SVI_TRY(run_block_self(h, 0, w.X, w.modf, L, st));
     if (stacked) {
         SVI_CHECK_HIP(hipMemcpyAsync(w.X + (size_t)L * D, w.X, (size_t)L * D * 2, hipMemcpyDeviceToDevice, st));
         CtxUse cu[2]{};
@@ -1074,6 +1103,8 @@ static svi_status forward_pair(svi_dit* h, const bf16* x, const float* timestep,
             CtxKV kvs[2] = {kv_of(h, cu[0], l), kv_of(h, cu[1], l)};
             SVI_TRY(run_block_rest_n(h, l, w.X, CTXs, modf, L, Lc, kvs, 2, st));
         }
+        if (tea_mode == 1)
+            for (int k = 0; k < 2; ++k) SVI_TRY(svi_launch_sub_bf16(ress[k], w.X + (size_t)k * L * D, w.X2, (int64_t)L * D, st));
         SVI_TRY(stage_head_rows(h, w.HO, 2 * L, st, 2));
         for (int k = 0; k < 2; ++k) SVI_TRY(stage_unpatchify(h, w.HO + (size_t)k * L * head_ld(c), outs[k], T, H, W, st));
         return SVI_OK;
@@ -1081,11 +1112,13 @@ static svi_status forward_pair(svi_dit* h, const bf16* x, const float* timestep,
     SVI_CHECK_HIP(hipMemcpyAsync(w.X2, w.X, (size_t)L * D * 2, hipMemcpyDeviceToDevice, st));
     for (int k = 0; k < 2; ++k) {
         if (k) SVI_CHECK_HIP(hipMemcpyAsync(w.X, w.X2, (size_t)L * D * 2, hipMemcpyDeviceToDevice, st));
+        if (k && tea_mode == 1) SVI_CHECK_HIP(hipMemcpyAsync(w.X2, res_b, xbytes, hipMemcpyDeviceToDevice, st));
         CtxUse cu{};
         SVI_TRY(stage_context(h, ctxs[k], clip, y, Lc, &cu, st));      // the CLIP branch has scratch rows of its own: X is untouched
         SVI_TRY(run_block_rest(h, 0, w.X, cu.CTXp, w.modf, L, Lc, kv_of(h, cu, 0), st));
         for (int l = 1; l < c.num_layers; ++l)
             SVI_TRY(run_block(h, l, w.X, cu.CTXp, w.modf + (size_t)l * 6 * D, L, Lc, kv_of(h, cu, l), st));
+        if (tea_mode == 1) SVI_TRY(svi_launch_sub_bf16(ress[k], w.X, k ? w.X2 : res_b, (int64_t)L * D, st));
         SVI_TRY(stage_head(h, outs[k], T, H, W, L, st));
     }
     return SVI_OK;
@@ -1179,16 +1212,20 @@ extern "C" svi_status svi_dit_time_mod(svi_dit* h, const float* timestep, void* 
     return SVI_OK;
 }
 
-extern "C" svi_status svi_dit_forward_cfg_pair(svi_dit* h, const void* x, const float* timestep, const void* context_cond,
-                                               const void* context_uncond, const void* clip_feature, const void* y,
-                                               const void* add_condition, void* out_cond, void* out_uncond, int32_t B, int32_t T,
-                                               int32_t H, int32_t W, int32_t Lc, svi_stream stream) {
+// svi_dit_forward_cfg_pair and svi_dit_forward_cfg_pair_tea: one body (tea_mode 0 is the plain pair)
+static svi_status cfg_pair_entry(svi_dit* h, const void* x, const float* timestep, const void* context_cond,
+                                 const void* context_uncond, const void* clip_feature, const void* y,
+                                 const void* add_condition, void* out_cond, void* out_uncond, int32_t B, int32_t T,
+                                 int32_t H, int32_t W, int32_t Lc, int32_t tea_mode, void* residual_cond, void* residual_uncond, svi_stream stream) {
     SVI_REQUIRE(h && x && timestep && context_cond && context_uncond && out_cond && out_uncond, "svi_dit_forward_cfg_pair: null argument");
     SVI_REQUIRE_DEVICE(h);
     SVI_REQUIRE(B > 0 && T > 0 && H > 0 && W > 0 && Lc > 0, "svi_dit_forward_cfg_pair: bad sizes");
     if (h->aud_first) { svi_set_error("svi_dit_forward_cfg_pair: the talk variant's branches differ in their audio; run them as separate forwards"); return SVI_ERR_UNSUPPORTED; }
     SVI_REQUIRE(y || h->cfg.in_dim == 16, "this model takes %d extra input channels: y must be given", h->cfg.in_dim - 16);
     SVI_REQUIRE(!h->cfg.has_image_input || clip_feature, "has_image_input model needs clip_feature");
+    SVI_REQUIRE(tea_mode >= 0 && tea_mode <= 2 && (tea_mode == 0 || (residual_cond && residual_uncond && residual_cond != residual_uncond)),
+                "svi_dit_forward_cfg_pair_tea: tea_mode %d needs one residual buffer per branch", tea_mode);
+    SVI_REQUIRE(tea_mode == 0 || (((uintptr_t)residual_cond | (uintptr_t)residual_uncond) & 15) == 0, "svi_dit_forward_cfg_pair_tea: the residual buffers must be 16-byte aligned");
     const svi_dit_config& c = h->cfg;
     SVI_REQUIRE(T % c.patch_t == 0 && H % c.patch_h == 0 && W % c.patch_w == 0,
                 "latent size %dx%dx%d is not divisible by the patch size", T, H, W);
@@ -1205,9 +1242,28 @@ extern "C" svi_status svi_dit_forward_cfg_pair(svi_dit* h, const void* x, const 
         const bf16* ab = add_condition ? reinterpret_cast<const bf16*>(add_condition) + (size_t)b * L * c.dim : nullptr;
         bf16* oa = reinterpret_cast<bf16*>(out_cond) + b * (size_t)c.out_dim * thw;
         bf16* ob = reinterpret_cast<bf16*>(out_uncond) + b * (size_t)c.out_dim * thw;
-        SVI_TRY(forward_pair(h, xb, timestep + b, ca, cbn, clb, yb, ab, oa, ob, T, H, W, Lc, st));
+        bf16* ra = tea_mode ? reinterpret_cast<bf16*>(residual_cond) + (size_t)b * L * c.dim : nullptr;
+        bf16* rb = tea_mode ? reinterpret_cast<bf16*>(residual_uncond) + (size_t)b * L * c.dim : nullptr;
+        SVI_TRY(forward_pair(h, xb, timestep + b, ca, cbn, clb, yb, ab, oa, ob, T, H, W, Lc, st, tea_mode, ra, rb));
     }
     return SVI_OK;
+}
+
+extern "C" svi_status svi_dit_forward_cfg_pair(svi_dit* h, const void* x, const float* timestep, const void* context_cond,
+                                               const void* context_uncond, const void* clip_feature, const void* y,
+                                               const void* add_condition, void* out_cond, void* out_uncond, int32_t B, int32_t T,
+                                               int32_t H, int32_t W, int32_t Lc, svi_stream stream) {
+    return cfg_pair_entry(h, x, timestep, context_cond, context_uncond, clip_feature, y, add_condition, out_cond, out_uncond, B, T, H, W, Lc, 0, nullptr, nullptr, stream);
+}
+
+// The CFG pair with TeaCache (svi_hip.h): store and skip for both branches in one call.
+extern "C" svi_status svi_dit_forward_cfg_pair_tea(svi_dit* h, const void* x, const float* timestep, const void* context_cond,
+                                                   const void* context_uncond, const void* clip_feature, const void* y,
+                                                   const void* add_condition, void* out_cond, void* out_uncond, int32_t B, int32_t T,
+                                                   int32_t H, int32_t W, int32_t Lc, int32_t tea_mode, void* residual_cond, void* residual_uncond,
+                                                   svi_stream stream) {
+    return cfg_pair_entry(h, x, timestep, context_cond, context_uncond, clip_feature, y, add_condition, out_cond, out_uncond, B, T, H, W, Lc, tea_mode,
+                          residual_cond, residual_uncond, stream);
 }
 
 // A rolling window hands the NEXT clip's prompt embedding (and CLIP feature) to the model in the SAME device tensors (the caller copied the new

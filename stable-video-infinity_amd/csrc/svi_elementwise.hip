@@ -550,6 +550,99 @@ svi_status svi_launch_add_bf16(bf16* a, const bf16* b, int64_t n, hipStream_t st
     return SVI_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// TeaCache skip step of a CFG pair (pipelines/svi_video.py:68-70, then the head's norm, models/wan_video_dit.py:401-404): both branches see the
+// same patch-embedded row of X and differ in their cached residual only.  One wave reads the row of X once and, per branch, the matching residual
+// row, forms bf16(x + residual) — add_bf16_kernel's rounding point — and writes that branch's LayerNorm + modulate row: X is left as it is, and the
+// add_bf16 pass over X and the separate LayerNorm launch per branch are gone (three row reads and two row writes instead of six and four).
+// The statistics and the output arithmetic are ln_mod_kernel's, statement for statement (sum over the lane's chunks in order, wave_sum, the same
+// rbf() points), so each output row has the bits of add_bf16 followed by svi_launch_ln_mod (either of its kernels: they agree bit for bit).
+// res_b / out_b may be null: one branch only.
+template <int MAXC>
+__global__ __launch_bounds__(256) void add_ln_mod_pair_kernel(const bf16* __restrict__ x, const bf16* __restrict__ res_a, const bf16* __restrict__ res_b,
+                                                              bf16* __restrict__ out_a, bf16* __restrict__ out_b, int rows, int dim, float eps,
+                                                              const float* __restrict__ shift, const float* __restrict__ scale1p) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int nchunk = dim >> 3;
+    const size_t roff = (size_t)row * dim;
+    bf16x8 xv[MAXC];
+#pragma unroll
+    for (int c = 0; c < MAXC; ++c) {
+        const int ci = lane + 64 * c;
+        if (ci < nchunk) xv[c] = ld_bf16x8(x + roff + ci * 8);
+    }
+#pragma unroll
+    for (int br = 0; br < 2; ++br) {
+        const bf16* res = br ? res_b : res_a;
+        bf16* out = br ? out_b : out_a;
+        if (!res) continue;                              // uniform over the grid
+        float v[MAXC][8];
+        float s = 0.f;
+#pragma unroll
+        for (int c = 0; c < MAXC; ++c) {
+            const int ci = lane + 64 * c;
+            if (ci < nchunk) {
+                const bf16x8 r = ld_bf16x8(res + roff + ci * 8);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) { v[c][j] = (float)(bf16)((float)xv[c][j] + (float)r[j]); s += v[c][j]; }
+            } else {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) v[c][j] = 0.f;
+            }
+        }
+        const float mean = wave_sum(s) / (float)dim;
+        float q = 0.f;
+#pragma unroll
+        for (int c = 0; c < MAXC; ++c) {
+            const int ci = lane + 64 * c;
+            if (ci < nchunk) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) { float d = v[c][j] - mean; q += d * d; }
+            }
+        }
+        const float rstd = rsqrtf(wave_sum(q) / (float)dim + eps);
+#pragma unroll
+        for (int c = 0; c < MAXC; ++c) {
+            const int ci = lane + 64 * c;
+            if (ci < nchunk) {
+                const int col = ci * 8;
+                const f32x4 sc0 = *reinterpret_cast<const f32x4*>(scale1p + col), sc1 = *reinterpret_cast<const f32x4*>(scale1p + col + 4);
+                const f32x4 sh0 = *reinterpret_cast<const f32x4*>(shift + col), sh1 = *reinterpret_cast<const f32x4*>(shift + col + 4);
+                bf16x8 o;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    float y = rbf((v[c][j] - mean) * rstd);
+                    y = rbf(rbf(y * (j < 4 ? sc0[j & 3] : sc1[j & 3])) + (j < 4 ? sh0[j & 3] : sh1[j & 3]));
+                    o[j] = (bf16)y;
+                }
+                st_bf16x8(out + roff + col, o);
+            }
+        }
+    }
+}
+
+// x, res_*, out_*: dense [rows, dim] bf16, 16-byte aligned; out_a / out_b are written, x and the residuals only read.
+svi_status svi_launch_add_ln_mod_pair(const bf16* x, const bf16* res_a, const bf16* res_b, bf16* out_a, bf16* out_b, int rows, int dim, float eps,
+                                      const float* shift, const float* scale1p, hipStream_t st) {
+    SVI_REQUIRE(x && res_a && out_a && shift && scale1p && (res_b == nullptr) == (out_b == nullptr), "add + layernorm: null operand");
+    SVI_REQUIRE(dim % 8 == 0 && dim <= 8192, "add + layernorm: dim %d must be a multiple of 8, at most 8192", dim);
+    SVI_REQUIRE((((uintptr_t)x | (uintptr_t)res_a | (uintptr_t)res_b | (uintptr_t)out_a | (uintptr_t)out_b | (uintptr_t)shift | (uintptr_t)scale1p) & 15) == 0,
+                "add + layernorm: operands must be 16-byte aligned");
+    if (rows <= 0) return SVI_OK;
+    dim3 grid((rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK), block(256);
+    const int nchunk = dim / 8;
+    if (nchunk <= 64 * 3)
+        hipLaunchKernelGGL(add_ln_mod_pair_kernel<3>, grid, block, 0, st, x, res_a, res_b, out_a, out_b, rows, dim, eps, shift, scale1p);
+    else if (nchunk <= 64 * 10)
+        hipLaunchKernelGGL(add_ln_mod_pair_kernel<10>, grid, block, 0, st, x, res_a, res_b, out_a, out_b, rows, dim, eps, shift, scale1p);
+    else
+        hipLaunchKernelGGL(add_ln_mod_pair_kernel<16>, grid, block, 0, st, x, res_a, res_b, out_a, out_b, rows, dim, eps, shift, scale1p);
+    SVI_LAUNCH_CHECK();
+    return SVI_OK;
+}
+
 
 // ------------------------------------------------------------------------------------------------
 // Frame hand-off of the clip loop, on the device.  The reference turns the decoded video into 8-bit frames

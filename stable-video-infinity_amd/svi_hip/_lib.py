@@ -67,6 +67,7 @@ SYMBOLS = [
     ("svi_dit_time_mod", _i32, [_vp, _vp, _vp, _i32, _vp]),
     ("svi_dit_forward_tea", _i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     ("svi_dit_forward_cfg_pair", _i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
+    ("svi_dit_forward_cfg_pair_tea", _i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     ("svi_dit_context_cache", _i32, [_vp, _i32]),
     ("svi_dit_context_refill", _i32, [_vp, _vp, _vp, _i32, _vp]),
     ("svi_linear_row_stats", _i32, [_vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _f32, _vp, _i32, _vp, _vp]),

@@ -385,9 +385,12 @@ class WanDiT:
     def forward_cfg_pair(self, x: torch.Tensor, timestep: torch.Tensor, context_cond: torch.Tensor, context_uncond: torch.Tensor,
                          clip_feature: Optional[torch.Tensor] = None, y: Optional[torch.Tensor] = None,
                          add_condition: Optional[torch.Tensor] = None, out_cond: Optional[torch.Tensor] = None,
-                         out_uncond: Optional[torch.Tensor] = None):
+                         out_uncond: Optional[torch.Tensor] = None, tea_mode: int = 0, residual_cond: Optional[torch.Tensor] = None,
+                         residual_uncond: Optional[torch.Tensor] = None):
         """Both forwards of a CFG step (svi_video.py:401-408) in one call: what precedes the first use of the prompt (timestep
-        embedding, patchify, block 0's self-attention) is computed once; outputs are bit-identical to two forward() calls."""
+        embedding, patchify, block 0's self-attention) is computed once; outputs are bit-identical to two forward() calls.
+        tea_mode / residual_cond / residual_uncond: TeaCache for both branches (svi_dit_forward_cfg_pair_tea), as forward()'s tea_mode / residual:
+        1 = also write each branch's residual [B, L, dim], 2 = skip the blocks and add each branch's residual instead (the prompts are not read)."""
         if not x.is_cuda:
             raise RuntimeError("svi_hip runs on the GPU only")
         if context_cond.shape != context_uncond.shape:
@@ -409,6 +412,16 @@ class WanDiT:
             out_cond = torch.empty((B, self.out_dim, T, H, W), dtype=torch.bfloat16, device=x.device)
         if out_uncond is None:
             out_uncond = torch.empty((B, self.out_dim, T, H, W), dtype=torch.bfloat16, device=x.device)
+        if tea_mode:
+            for residual in (residual_cond, residual_uncond):
+                if residual is None or not residual.is_cuda or residual.dtype != torch.bfloat16 or not residual.is_contiguous() \
+                        or residual.numel() != B * self.tokens(T, H, W) * self.dim:
+                    raise ValueError("tea_mode needs a contiguous CUDA bf16 residual of shape [B, L, dim] per branch")
+            L.check(L.lib().svi_dit_forward_cfg_pair_tea(self._h, L.ptr(x), L.ptr(timestep), L.ptr(context_cond), L.ptr(context_uncond),
+                                                         L.ptr(clip_feature), L.ptr(y), L.ptr(add_condition), L.ptr(out_cond), L.ptr(out_uncond),
+                                                         B, T, H, W, context_cond.shape[1], int(tea_mode), L.ptr(residual_cond), L.ptr(residual_uncond),
+                                                         L.current_stream()), "svi_dit_forward_cfg_pair_tea")
+            return out_cond, out_uncond
         L.check(L.lib().svi_dit_forward_cfg_pair(self._h, L.ptr(x), L.ptr(timestep), L.ptr(context_cond), L.ptr(context_uncond),
                                                  L.ptr(clip_feature), L.ptr(y), L.ptr(add_condition), L.ptr(out_cond), L.ptr(out_uncond),
                                                  B, T, H, W, context_cond.shape[1], L.current_stream()), "svi_dit_forward_cfg_pair")

@@ -39,6 +39,12 @@ def _release_stream_buffers(stream) -> bool:
         return False
 
 
+# TeaCache steps under `graph=None` (the default) take the graphed path, as every other step of the single-rank loop does; `graph=False` keeps the eager
+# path through model_fn_wan_video.  Decided by the alternating A/B of tools/teacache_graph_ab.py: the clip median is lower at the C1 and at the C2 size
+# (profiles/teacache_graph_ab.txt).
+TEA_GRAPH_BY_DEFAULT = True
+
+
 class DenoiseLoop:
     """50 x { cond forward, uncond forward, CFG combine, Euler step } with latents resident in HBM."""
 
@@ -51,9 +57,14 @@ class DenoiseLoop:
         later step of the clip — the ~1500 launches of a step become one; the timestep is read from a device scalar that is
         refreshed before each replay.  Decisive where a step is launch-bound (BASELINE configs[0]: 1280 tokens), still 1.1 % at the
         C2 size (profiles/r3m_prof_events_ab.txt); results are bit-identical (the same kernels on the same operands).  Single-rank
-        path without TeaCache only.  Default (None): ON for the single-rank loop, off with a CFG pair / sequence parallelism (their
+        path only.  Default (None): ON for the single-rank loop, off with a CFG pair / sequence parallelism (their
         exchanges are host-driven).  The first step of a clip runs eagerly on the capture stream — it IS that step — and is recorded
         right behind itself; steps 2.. replay.
+        With TeaCache (step()'s tea_cache_posi / _nega) a graphed loop keeps its fast path: the skip decisions are taken on the host from t_mod, as
+        ever, and the step's device work — one forward_cfg_pair(tea_mode) call, or two forward(tea_mode) calls where the branches cannot share — is
+        captured once per mode (computed / skipped) and replayed; a resident loop stays resident.  Bit-identical to the eager TeaCache path
+        (tests/test_gpu_teacache_graph.py).  `graph=True` selects it, `graph=False` keeps the eager path through model_fn_wan_video; under
+        `graph=None` TEA_GRAPH_BY_DEFAULT decides (profiles/teacache_graph_ab.txt).
         `resident` (the rolling-window drivers turn it on: StreamLoop, install()'s sampler, bench.py --window): the loop OWNS the device tensors
         a clip's steps read — latents, the two prompt embeddings, clip_feature, y, add_condition — and every clip's inputs are copied into them
         (adopt()).  A clip boundary then moves no address: the prompt's cache entries are recomputed in place (WanDiT.refill_context) and the step
@@ -69,24 +80,62 @@ class DenoiseLoop:
             raise ValueError("graph capture covers the single-rank step only")
         self.graph = (cfg_pair is None and not sequence_parallel) if graph is None else bool(graph)
         self.resident = bool(resident) and self.graph
+        self.tea_graph = self.graph and (TEA_GRAPH_BY_DEFAULT if graph is None else True)      # TeaCache steps on the graphed path (else: model_fn_wan_video)
         self._slots: Dict[str, torch.Tensor] = {}      # resident: name -> the loop's own tensor of that input
         self._slot_src: Dict[str, tuple] = {}          # name -> (the tensor last copied in — kept alive so that its address cannot return as another's —, its version)
         self.last_sp_form = None      # sequence-parallel steps: "stacked pair" (forward_distributed_pair) or "two forwards"
         self.captures = 0             # how many times a step was captured (a resident stream of equal-shaped clips: once)
         self._graph = None            # dict(key, graph, ts, pins, generation) of the captured step, see _forwards_graphed
+        self._tea_graphs: Dict[tuple, dict] = {}      # TeaCache: (mode of the conditional branch, of the unconditional) -> the same dict; at most two alive
+        self._tea_res: Dict[str, torch.Tensor] = {}   # the loop's residual tensor per branch (a resident loop keeps them in _slots: their addresses survive a clip boundary)
+        self.tea_counts = {"computed": 0, "skipped": 0}      # TeaCache steps since the last sample() began, by the conditional branch's decision
         self._capture_stream = None   # ONE side stream per loop, reused by every re-capture: the library keeps per-stream scratch (flag words,
                                       # split-K partials) for good, so a fresh pool stream per capture would multiply it
 
-    def _forwards(self, latents, timestep, ctx_pos, ctx_neg, cfg_scale, split, cond, ucond) -> None:
-        """The DiT forward(s) of one step into self._cond / self._uncond."""
+    def _forwards(self, latents, timestep, ctx_pos, ctx_neg, cfg_scale, split, cond, ucond, tea=None) -> None:
+        """The DiT forward(s) of one step into self._cond / self._uncond.  `tea`: (tea_mode, residual) of the conditional branch, then of the unconditional
+        one (_tea_decide) — one pair call when the branches can share and decided alike, else one forward per branch with its own mode."""
+        mc, rc, mu, ru = tea or (0, None, 0, None)
+        tc = dict(tea_mode=mc, residual=rc) if mc else {}
         if cfg_scale != 1.0:
-            if ctx_neg.shape == ctx_pos.shape and not split:      # one call: the prompt-independent head of the forward is shared, results unchanged
-                self.dit.forward_cfg_pair(latents, timestep, ctx_pos, ctx_neg, out_cond=self._cond, out_uncond=self._uncond, **cond)
+            if ctx_neg.shape == ctx_pos.shape and not split and mc == mu:      # one call: the prompt-independent head of the forward is shared, results unchanged
+                tp = dict(tea_mode=mc, residual_cond=rc, residual_uncond=ru) if mc else {}
+                self.dit.forward_cfg_pair(latents, timestep, ctx_pos, ctx_neg, out_cond=self._cond, out_uncond=self._uncond, **tp, **cond)
             else:
-                self.dit.forward(latents, timestep, ctx_pos, out=self._cond, **cond)
-                self.dit.forward(latents, timestep, ctx_neg, out=self._uncond, **ucond)
+                tu = dict(tea_mode=mu, residual=ru) if mu else {}
+                self.dit.forward(latents, timestep, ctx_pos, out=self._cond, **tc, **cond)
+                self.dit.forward(latents, timestep, ctx_neg, out=self._uncond, **tu, **ucond)
         else:
-            self.dit.forward(latents, timestep, ctx_pos, out=self._cond, **cond)
+            self.dit.forward(latents, timestep, ctx_pos, out=self._cond, **tc, **cond)
+
+    def _tea_residual(self, name: str, shape, device) -> torch.Tensor:
+        """The loop's own residual tensor of one branch; in resident mode a slot (kept from clip to clip, so a captured step's addresses hold)."""
+        store, key = (self._slots, "tea_residual_" + name) if self.resident else (self._tea_res, name)
+        res = store.get(key)
+        if res is None or tuple(res.shape) != tuple(shape) or res.device != device:
+            res = store[key] = torch.empty(shape, dtype=torch.bfloat16, device=device)
+        return res
+
+    def _tea_decide(self, latents, timestep, caches):
+        """The TeaCache decisions of one step, on the host, before anything of the step is enqueued: each object's own check(dit, token, t_mod)
+        (svi_hip.TeaCache or the reference's class, svi_video.py:43-62) on this step's t_mod.  Returns (mode, residual) per branch, flattened:
+        2 + the object's previous_residual for a skip, 1 + the loop's residual tensor of that branch for a computed step, (0, None) without an object."""
+        t_mod = self.dit.time_mod(timestep)
+        B, _, T, H, W = latents.shape
+        shape = (B, self.dit.tokens(T, H, W), self.dit.dim)
+        out = []
+        for name, cache in zip(("cond", "uncond"), caches):
+            if cache is None:
+                out += [0, None]
+            elif cache.check(self.dit, t_mod[:, :1, :1], t_mod):      # the token: check() keeps `x` only for a residual that is formed on the device here
+                res = cache.previous_residual
+                if res is None:
+                    raise RuntimeError("TeaCache asked to skip before any residual was stored")
+                out += [2, res]
+            else:
+                out += [1, self._tea_residual(name, shape, latents.device)]
+        self.tea_counts["skipped" if out[0] == 2 else "computed"] += 1
+        return tuple(out)
 
     def adopt(self, latents: torch.Tensor, ctx_pos: torch.Tensor, ctx_neg: Optional[torch.Tensor], cond: dict):
         """Resident mode: copy one clip's inputs into the loop's own tensors and return those (latents, ctx_pos, ctx_neg, cond).  A tensor whose
@@ -135,6 +184,7 @@ class DenoiseLoop:
     def close(self) -> None:
         """End of a resident stream: the captured step, the slots and the context cache go."""
         self._graph = None
+        self._tea_graphs.clear()
         self._slots, self._slot_src = {}, {}
         if self.resident and self.dit._ctx_cache_on:
             self.dit.context_cache(False)
@@ -143,6 +193,7 @@ class DenoiseLoop:
     def drop_graph(self) -> None:
         """Forget the captured step (a later graphed step captures again)."""
         self._graph = None
+        self._tea_graphs.clear()
 
     def _retire_capture_stream(self) -> bool:
         """Release the library's per-stream buffers of this loop's capture stream and forget the stream.  When the release cannot happen now (another loop's
@@ -164,9 +215,24 @@ class DenoiseLoop:
         """Retire this loop's capture stream: the captured step and the library's per-stream buffers keyed to that stream are freed
         (also done when the loop is garbage-collected)."""
         self._graph = None
+        self._tea_graphs.clear()
         self._retire_capture_stream()
 
-    def _forwards_graphed(self, latents, timestep, ctx_pos, ctx_neg, cfg_scale, split, cond, ucond) -> None:
+    def _graph_key(self, latents, ctx_pos, ctx_neg, cfg_scale, split, cond, tea=None):
+        """(slot, key, tensors) of a step's captured graph: which graph of the loop serves the step (None: the plain step; with TeaCache the pair of
+        the branches' modes), what must still hold for a replay, and the tensors the graph pins.  See _forwards_graphed."""
+        def ident(t):      # the loop's own tensors (resident mode) are rewritten by adopt() between clips: their version is not part of the key
+            return None if t is None else (t.data_ptr(), tuple(t.shape), t.dtype, -1 if self._owned(t) else _version(t))
+        tensors = [latents, ctx_pos, ctx_neg, self._cond, self._uncond] + [v for _, v in sorted(cond.items()) if isinstance(v, torch.Tensor)]
+        slot = None if tea is None else (tea[0], tea[2])
+        residuals = [] if tea is None else [tea[1], tea[3]]
+        key = (tuple(ident(t) for t in tensors), tuple(sorted((k, None if isinstance(v, torch.Tensor) else repr(v)) for k, v in cond.items() if v is not None)),
+               float(cfg_scale), bool(split), self.dit.epoch(), L.switch_epoch())
+        if tea is not None:
+            key += (slot, tuple(None if r is None else (r.data_ptr(), tuple(r.shape), r.dtype) for r in residuals))
+        return slot, key, tensors + [r for r in residuals if r is not None]
+
+    def _forwards_graphed(self, latents, timestep, ctx_pos, ctx_neg, cfg_scale, split, cond, ucond, tea=None) -> None:
         """Replay (capture on first use) the hipGraph of this step's forwards.
 
         A captured graph has baked in the ADDRESSES of everything it reads and writes (latents, prompt embeddings, conditioning
@@ -178,16 +244,20 @@ class DenoiseLoop:
             (svi_dit_generation: workspace growth, a context entry filled or evicted) as read right after the capture;
           * the key carries the count of in-process switch reloads (_lib.set_switch): a graph recorded under other library switches is not replayed;
           * sample() drops the graph when the clip is done.
-        Anything else re-captures."""
-        def ident(t):      # the loop's own tensors (resident mode) are rewritten by adopt() between clips: their version is not part of the key
-            return None if t is None else (t.data_ptr(), tuple(t.shape), t.dtype, -1 if self._owned(t) else _version(t))
+        Anything else re-captures.
+        TeaCache (`tea`, see _forwards): a computed step and a skipped step are different device work, so each mode — the pair (mode of the conditional
+        branch, mode of the unconditional one) — has a captured graph of its own, under the same rules; the key also carries the residual tensors'
+        identities (their contents are the graphs' business: the store graph writes them, the skip graph reads them).  Two are kept at the most, and
+        capturing one mode leaves the other's graph alone."""
         self.dit._refresh_if_weights_changed()          # a LoRA merge since the last step re-binds (and moves the epoch) BEFORE the key is formed
-        tensors = [latents, ctx_pos, ctx_neg, self._cond, self._uncond] + [v for _, v in sorted(cond.items()) if isinstance(v, torch.Tensor)]
-        key = (tuple(ident(t) for t in tensors), tuple(sorted((k, None if isinstance(v, torch.Tensor) else repr(v)) for k, v in cond.items() if v is not None)),
-               float(cfg_scale), bool(split), self.dit.epoch(), L.switch_epoch())
-        stale = self._graph is None or self._graph["key"] != key or self._graph["generation"] != self.dit.generation()
+        slot, key, tensors = self._graph_key(latents, ctx_pos, ctx_neg, cfg_scale, split, cond, tea)
+        held = self._graph if slot is None else self._tea_graphs.get(slot)
+        stale = held is None or held["key"] != key or held["generation"] != self.dit.generation()
         if stale:
-            self._graph = None
+            if slot is None:
+                self._graph = None
+            else:
+                self._tea_graphs.pop(slot, None)
             if self._capture_stream is None or self._capture_stream.device != latents.device:
                 self._retire_capture_stream()
                 self._capture_stream = torch.cuda.Stream(device=latents.device)
@@ -201,32 +271,42 @@ class DenoiseLoop:
             with torch.cuda.stream(side):
                 # this step itself, eagerly: it also sizes the workspaces, fills the context cache and creates the flag words,
                 # so that the recording below allocates nothing
-                self._forwards(latents, ts_static, ctx_pos, ctx_neg, cfg_scale, split, cond, ucond)
+                self._forwards(latents, ts_static, ctx_pos, ctx_neg, cfg_scale, split, cond, ucond, tea)
             side.synchronize()
             g = torch.cuda.CUDAGraph()
             # recorded, not executed: self._cond / self._uncond keep the eager step's results.  thread_local: other threads of the process (a
             # communicator's watchdog, a data loader) are not bound by this capture's rules
             with torch.cuda.graph(g, stream=side, capture_error_mode="thread_local"):
-                self._forwards(latents, ts_static, ctx_pos, ctx_neg, cfg_scale, split, cond, ucond)
+                self._forwards(latents, ts_static, ctx_pos, ctx_neg, cfg_scale, split, cond, ucond, tea)
             torch.cuda.current_stream().wait_stream(side)
-            self._graph = dict(key=key, graph=g, ts=ts_static, pins=tensors, generation=self.dit.generation())
+            held = dict(key=key, graph=g, ts=ts_static, pins=tensors, generation=self.dit.generation())
+            if slot is None:
+                self._graph = held
+                self._tea_graphs.clear()                 # a loop is used with TeaCache or without: the other kind's graphs go
+            else:
+                self._graph = None
+                while len(self._tea_graphs) >= 2:        # caches that disagree can ask for a third mode: the oldest goes
+                    self._tea_graphs.pop(next(iter(self._tea_graphs)))
+                self._tea_graphs[slot] = held
             self.captures += 1
             return
-        self._graph["ts"].copy_(timestep)
-        self._graph["graph"].replay()
+        held["ts"].copy_(timestep)
+        held["graph"].replay()
 
     def step(self, latents: torch.Tensor, timestep: torch.Tensor, dsigma: float, ctx_pos: torch.Tensor,
              ctx_neg: Optional[torch.Tensor], cfg_scale: float, tea_cache_posi=None, tea_cache_nega=None, cond_wo_pose: bool = False,
              **cond) -> torch.Tensor:
         """One scheduler step, in place on `latents` (bf16 [B,16,T,H,W]).  tea_cache_posi / _nega: one TeaCache per CFG branch
-        (svi_video.py:500-501); with them the two forwards go through model_fn_wan_video separately, as in the reference.
+        (svi_video.py:500-501).  On a loop with `tea_graph` (see __init__) their decisions are taken first (_tea_decide) and the step runs on the loop's
+        own path — graphed, the pair in one call, resident; previous_residual / previous_hidden_states end as model_fn_wan_video leaves them.  Otherwise
+        (graph=False, a CFG pair, sequence parallelism) the two forwards go through model_fn_wan_video separately, as in the reference.
         `add_condition` (in **cond; the dance variant's pose embedding) goes to the conditional forward only, unless `cond_wo_pose`
         (SVIDanceVideoPipeline._sample_with_dance_video, svi_video_dance.py:423-430)."""
         ucond = cond                                # keyword inputs of the unconditional forward
         if cond.get("add_condition") is not None and not cond_wo_pose:
             ucond = dict(cond, add_condition=None)
         split = ucond is not cond                   # the two branches differ in more than the prompt
-        if tea_cache_posi is not None:
+        if tea_cache_posi is not None and not self.tea_graph:
             from .dit import model_fn_wan_video
             usp = {}
             if self.sequence_parallel:          # as the reference: TeaCache + USP (svi_video.py:112-131), residuals per rank
@@ -281,7 +361,16 @@ class DenoiseLoop:
             self._cond = torch.empty_like(latents)
             self._uncond = torch.empty_like(latents)
         run = self._forwards_graphed if self.graph else self._forwards
-        run(latents, timestep, ctx_pos, ctx_neg, cfg_scale, split, cond, ucond)
+        if tea_cache_posi is not None:
+            caches = (tea_cache_posi, tea_cache_nega if cfg_scale != 1.0 else None)
+            tea = self._tea_decide(latents, timestep, caches)
+            run(latents, timestep, ctx_pos, ctx_neg, cfg_scale, split, cond, ucond, tea)
+            for cache, mode, res in zip(caches, tea[0::2], tea[1::2]):
+                if mode == 1:                          # what TeaCache.store() would have computed (svi_video.py:64-66), as model_fn_wan_video leaves it
+                    cache.previous_residual = res
+                    cache.previous_hidden_states = None
+        else:
+            run(latents, timestep, ctx_pos, ctx_neg, cfg_scale, split, cond, ucond)
         if cfg_scale != 1.0:
             ops.cfg_step_(latents, self._cond, self._uncond, cfg_scale, dsigma)
         else:
@@ -340,7 +429,8 @@ class DenoiseLoop:
             tea = dict(tea_cache_posi=TeaCache(num_inference_steps, tea_cache_l1_thresh, tea_cache_model_id),
                        tea_cache_nega=TeaCache(num_inference_steps, tea_cache_l1_thresh, tea_cache_model_id))
         ts_dev = self.scheduler.timesteps.to(device=latents.device, dtype=torch.float32)
-        resident = self.resident and not tea
+        self.tea_counts = {"computed": 0, "skipped": 0}
+        resident = self.resident and (not tea or self.tea_graph)
         if resident:
             # the clip's inputs go into the loop's own tensors; the context cache stays on from clip to clip (entries recomputed in place)
             if not self.dit._ctx_cache_on:
@@ -453,7 +543,7 @@ def _hip_sample_with_regular_video(self, latents, prompt_emb_posi, prompt_emb_ne
     tea = {}
     if (tea_cache_posi or {}).get("tea_cache") is not None:
         tea = dict(tea_cache_posi=tea_cache_posi["tea_cache"], tea_cache_nega=(tea_cache_nega or {}).get("tea_cache"))
-    resident = loop.resident and not tea
+    resident = loop.resident and (not tea or loop.tea_graph)
     cond = {k: image_emb[k] for k in ("clip_feature", "y") if image_emb.get(k) is not None}
     if resident:
         # the rolling window re-enters __call__ per clip (test_svi.py:424-476): each clip's latents / prompt / conditioning are copied into the loop's
@@ -535,7 +625,7 @@ def _hip_wan_pipeline_call(self, *args, **kwargs):
             mk = lambda: TC(p["num_inference_steps"], rel_l1_thresh=p["tea_cache_l1_thresh"], model_id=p.get("tea_cache_model_id", ""))      # noqa: E731
             tea = dict(tea_cache_posi=mk(), tea_cache_nega=mk())
         cond = {k: img[k] for k in ("clip_feature", "y") if img.get(k) is not None}
-        resident = loop.resident and not tea
+        resident = loop.resident and (not tea or loop.tea_graph)
         ctx_n = nega["context"] if cfg_scale != 1.0 else None
         if resident:
             x, ctx_p, ctx_n, cond = loop.adopt(lat, posi["context"], ctx_n, cond)

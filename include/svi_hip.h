@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define SVI_HIP_ABI_VERSION 12
+#define SVI_HIP_ABI_VERSION 13
 
 typedef enum {
     SVI_OK = 0,
@@ -329,6 +329,19 @@ svi_status svi_gemm_bf16(const void* A, int32_t lda, const void* W, int32_t ldw,
                          int32_t M, int32_t N, int32_t K, const void* bias, int32_t bias_along_m,
                          int32_t epilogue, const float* gate, const void* res, int32_t ldres,
                          svi_stream stream);
+/* ABI v13 — the same GEMM as the DiT block launches it for q | k and for the stacked CFG pair: svi_gemm_bf16's arguments plus
+ *   W2, bias2, n_split   two weight matrices side by side in the output: columns [0, n_split) come from W [n_split, ldw] and bias, columns [n_split, N)
+ *                        from W2 [N - n_split, ldw] and bias2 (bf16 [N - n_split] or NULL).  gate, res and C span all N columns.  One launch when
+ *                        n_split is a multiple of the tile width of the kernel that runs (128, 192 or 256), else one launch per matrix — the same bits
+ *                        either way, and the same as two svi_gemm_bf16 calls on the halves.  W2 NULL: one matrix, n_split and bias2 ignored.
+ *                        Refused: n_split <= 0 or >= N, n_split not a multiple of 8, bias_along_m with W2.
+ *   sel_m, sel_n         > 0: choose the kernel as svi_gemm_plan would for a problem of sel_m rows / sel_n columns (samples stacked along M or N keep the
+ *                        kernel of a per-sample launch); 0: by M / N. */
+svi_status svi_gemm_bf16_pair(const void* A, int32_t lda, const void* W, int32_t ldw, void* C, int32_t ldc,
+                              int32_t M, int32_t N, int32_t K, const void* bias, int32_t bias_along_m,
+                              int32_t epilogue, const float* gate, const void* res, int32_t ldres,
+                              const void* W2, const void* bias2, int32_t n_split, int32_t sel_m, int32_t sel_n,
+                              svi_stream stream);
 
 /* ---- MX-fp8 (opt-in; north_star "bf16/fp8 MFMA").  The reference computes in bf16 and only STORES weights as float8_e4m3fn
  * (test_svi.py:337, vram_management/layers.py:65-71): what follows is arithmetic it never performs — own tolerance, own bench line.

@@ -486,6 +486,22 @@ extern "C" svi_status svi_gemm_bf16(const void* A, int32_t lda, const void* W, i
     return svi_launch_gemm(g, reinterpret_cast<hipStream_t>(stream));
 }
 
+// svi_gemm_bf16 with the fields the DiT block sets for its q | k projection (two weights side by side) and for stacked samples (the per-sample kernel choice)
+extern "C" svi_status svi_gemm_bf16_pair(const void* A, int32_t lda, const void* W, int32_t ldw, void* C, int32_t ldc, int32_t M,
+                                         int32_t N, int32_t K, const void* bias, int32_t bias_along_m, int32_t epilogue,
+                                         const float* gate, const void* res, int32_t ldres, const void* W2, const void* bias2,
+                                         int32_t n_split, int32_t sel_m, int32_t sel_n, svi_stream stream) {
+    SVI_REQUIRE(A && W && C, "svi_gemm_bf16_pair: null argument");
+    SviGemmArgs g{};
+    g.A = reinterpret_cast<const bf16*>(A); g.lda = lda; g.W = reinterpret_cast<const bf16*>(W); g.ldw = ldw;
+    g.C = reinterpret_cast<bf16*>(C); g.ldc = ldc; g.M = M; g.N = N; g.K = K;
+    g.bias = reinterpret_cast<const bf16*>(bias); g.bias_along_m = bias_along_m; g.epi = epilogue; g.gate = gate;
+    g.res = reinterpret_cast<const bf16*>(res); g.ldres = ldres;
+    if (W2) { g.W2 = reinterpret_cast<const bf16*>(W2); g.bias2 = reinterpret_cast<const bf16*>(bias2); g.n_split = n_split; }
+    g.sel_m = sel_m; g.sel_n = sel_n;
+    return svi_launch_gemm(g, reinterpret_cast<hipStream_t>(stream));
+}
+
 // The cross-attention query path as the DiT block runs it, in two seams (CrossAttention.forward, models/wan_video_dit.py:266-303: q = norm_q(self.q(x)), then
 // attention against the prompt's K / V): the projection that also leaves the RMSNorm statistic, and the short-key attention that normalises q as it reads it.
 extern "C" svi_status svi_linear_row_stats(const void* A, int32_t lda, const void* W, int32_t ldw, void* C, int32_t ldc, int32_t M, int32_t N, int32_t K,

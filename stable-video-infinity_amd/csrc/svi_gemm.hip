@@ -98,7 +98,7 @@ __global__ __launch_bounds__(NT, (PF == 1 && NT == 256) ? 2 : 1) void gemm_bf16_
         a_ok[j] = (m0 + r) < g.M;
         w_ok[j] = (n0 + r) < g.N;
         a_ptr[j] = g.A + (size_t)(a_ok[j] ? (m0 + r) : 0) * g.lda + ld_chunk * 8;
-        w_ptr[j] = g.W + (size_t)(w_ok[j] ? (n0 + r) : 0) * g.ldw + ld_chunk * 8;
+        w_ptr[j] = g.W + (size_t)(w_ok[j] ? (n0 + r) : n0) * g.ldw + ld_chunk * 8;          // (n0, not 0: row 0 of a base moved back for W2 lies before W2)
     }
     const int nk = (g.K + BK - 1) / BK;
     u32x4 ra[PF][LJ], rw[PF][LJ];
@@ -1165,6 +1165,8 @@ svi_status svi_launch_gemm(const SviGemmArgs& g, hipStream_t st) {
                     "gemm: row statistics need a tiled kernel, N %% 64 == 0 (N = %d), the plain bias epilogue and ldss >= M", g.N);
     if (g.W2) {        // two weight matrices side by side: one launch when the split falls on a tile boundary of the kernel that runs, else two
         SVI_REQUIRE(g.n_split > 0 && g.n_split < g.N && !g.bias_along_m && ((uintptr_t)g.W2 % 16) == 0, "gemm: bad weight pair (n_split %d of N %d)", g.n_split, g.N);
+        // (before anything is launched: the two-launch form below would write the first half and then refuse the second for its misaligned C)
+        SVI_REQUIRE(g.n_split % 8 == 0, "gemm: n_split %d of a weight pair must be a multiple of 8", g.n_split);
         // tiles of the second half read rows n - n_split of W2 through a base moved back by n_split rows and a descriptor sized for N rows from there: the
         // second matrix must hold N - n_split rows of the same stride (the DiT's q | k: two [D, D] weights), and its own 2^31-element bound holds with A / W's
         SVI_REQUIRE((long)(g.N - g.n_split) * g.ldw < (1L << 31), "gemm: second weight matrix of 2^31 elements or more");

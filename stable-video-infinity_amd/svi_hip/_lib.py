@@ -78,6 +78,7 @@ SYMBOLS = [
     ("svi_rmsnorm_rope", _i32, [_vp, _i32, _i32, _i32, _vp, _f32, _i32, _i32, _i32, _i32, _i32, _vp]),
     ("svi_rmsnorm_rope_qk", _i32, [_vp, _i32, _i32, _i32, _vp, _vp, _f32, _f32, _f32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     ("svi_gemm_bf16", _i32, [_vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _i32, _vp]),
+    ("svi_gemm_bf16_pair", _i32, [_vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp]),
     ("svi_cfg_step", _i32, [_vp, _vp, _vp, _i64, _f32, _f32, _vp]),
     ("svi_mx8_quantize", _i32, [_vp, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _vp]),
     ("svi_gemm_mx8", _i32, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _vp]),

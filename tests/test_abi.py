@@ -30,13 +30,17 @@ def test_ctypes_table_matches_header():
     assert sorted(n for n, _, _ in L.SYMBOLS) == declared_symbols()
 
 
-def test_abi_version_is_v12_in_header_and_library():
-    """v12 added the DiT's q | k RMSNorm + RoPE launch as an operator seam (svi_rmsnorm_rope_qk), v11 the VAE convolution planners
-    (svi_vae_conv_plan, svi_vae_tile_order); the header's define and the built library agree."""
+def test_abi_version_is_v13_in_header_and_library():
+    """v13 added the DiT's q | k projection launch (two weights side by side, the per-sample kernel choice) as an operator seam (svi_gemm_bf16_pair),
+    v12 its q | k RMSNorm + RoPE launch (svi_rmsnorm_rope_qk), v11 the VAE convolution planners (svi_vae_conv_plan, svi_vae_tile_order); the header's
+    define and the built library agree."""
     m = re.search(r"#define\s+SVI_HIP_ABI_VERSION\s+(\d+)", open(HEADER).read())
-    assert m and int(m.group(1)) == 12
-    assert L.lib().svi_abi_version() == 12
-    assert {"svi_vae_conv_plan", "svi_vae_tile_order", "svi_rmsnorm_rope_qk"} <= set(declared_symbols())
+    assert m and int(m.group(1)) == 13
+    assert L.lib().svi_abi_version() == 13
+    assert {"svi_vae_conv_plan", "svi_vae_tile_order", "svi_rmsnorm_rope_qk", "svi_gemm_bf16_pair"} <= set(declared_symbols())
+    # the pair entry point is svi_gemm_bf16's argument list with W2, bias2, n_split, sel_m, sel_n in front of the stream
+    table = {n: a for n, _, a in L.SYMBOLS}
+    assert table["svi_gemm_bf16_pair"] == table["svi_gemm_bf16"][:-1] + [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
 
 
 def test_dit_handle_lifecycle_and_errors():

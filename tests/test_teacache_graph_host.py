@@ -32,9 +32,9 @@ def test_pair_tea_entry_is_declared_exported_and_typed():
     assert fn(*([None] * 10), 1, 1, 1, 1, 1, 1, None, None, None) == 1 and "null argument" in L.last_error()      # host-side refusal, no device touched
 
 
-def test_abi_is_still_v12():
+def test_abi_is_v13():
     m = re.search(r"#define\s+SVI_HIP_ABI_VERSION\s+(\d+)", open(HEADER).read())
-    assert m and int(m.group(1)) == 12 and L.lib().svi_abi_version() == 12
+    assert m and int(m.group(1)) == 13 and L.lib().svi_abi_version() == 13
 
 
 # ---- step()'s mode selection ---------------------------------------------------------------------------------------------------------

@@ -128,11 +128,42 @@ svi_status svi_dit_forward(svi_dit* h, const void* x, const float* timestep, con
  * svi_dit_set_audio arms the handle for the following forwards (svi_dit_forward / _forward_tea, and sequence shards: svi_dit_sp_begin projects
  * the audio tokens of ALL latent frames on every rank, and a shard's rows — which may start and end inside a frame — attend to their own frames'
  * tokens through svi_attention_frames_fwd's kernel, the single-rank bits; the CFG pair, svi_dit_forward_cfg_pair and svi_dit_sp_begin_pair, refuses
- * while audio is set: its branches differ in their audio) and NULL pointers disarm it:
+ * while audio is set: its branches differ in their audio — the three guidance forwards of a talk step are svi_dit_forward_talk3) and NULL pointers
+ * disarm it:
  *   audio_first  bf16 [1, seq_len = 5, 12, 768]          the first frame's audio window          (audio_embed_tuple[0])
  *   audio_latter bf16 [T - 1, seq_len_vf = 8, 12, 768]   the later latent frames' windows        (audio_embed_tuple[1])
  * The pointers are borrowed until the next svi_dit_set_audio. */
 svi_status svi_dit_set_audio(svi_dit* h, const void* audio_first, const void* audio_latter, int32_t n_latter);
+
+/* The talk step as ONE call (additive in v13): the three guidance forwards of SVITalkVideoPipeline._sample_with_multitalk (svi_video_talk.py:455-458).
+ *
+ * svi_dit_audio_slot projects one clip's audio windows (shapes as svi_dit_set_audio) through AudioProjModel and through EVERY block's
+ * audio_cross_attn.kv_linear into buffers the slot owns: AUD [f * 32, 768] and, per layer, K [f * 32, dim] and V^T [dim, ld] — the launches an armed
+ * forward makes per forward and block, so the bits are a forward's.  They depend on (audio, weights) alone.  slot 0 = the clip's audio, 1 = the null
+ * audio.  Stream-ordered; the caller's pointers are read by the work this call enqueues and are NOT borrowed.  The first staging of a slot, or one
+ * with another frame count, allocates and moves svi_dit_generation (refused while the stream is being captured); a re-staging with the same frame count
+ * rewrites the buffers in place — no address and no generation moves: the clip boundary of a resident loop, as svi_dit_context_refill is for the
+ * prompt.  audio_first == NULL frees the slot (the generation moves).  Binding a weight drops both slots, as it drops the context cache.
+ * Memory: per slot num_layers x 2 x (f * 32) x dim x 2 B — 40 x 2 x 672 x 5120 x 2 B = 0.55 GB at the 14B width with 21 latent frames, 1.1 GB for
+ * the two slots a talk step needs.
+ *
+ * svi_dit_forward_talk3 runs, for one sample,
+ *     out_cond      = forward(context_cond,   audio slot 0, add_condition)
+ *     out_uncond    = forward(context_uncond, audio slot 1, no add_condition)
+ *     out_drop_text = forward(context_uncond, audio slot 0, add_condition)
+ * with the timestep embedding and modulation rows, patchify and the patch embedding computed once (the add_condition rows are added to a copy), block
+ * 0's self-attention third once per distinct embedded input (one run when add_condition is NULL, else two: cond and drop-text share), and every
+ * block's audio K / V^T read from the slots.  The branches then run one after another on the L-row workspace (three stacked branches would pass the
+ * stacked form's 2 GiB bound at the talk model's size).  Each output is bit-identical to svi_dit_forward with that branch's audio armed.  Works with
+ * the context cache on or off.  Once the slots are staged and a first call has sized the workspace (and, cache on, filled the prompts' entries) a call
+ * allocates nothing and does not synchronise: it can be captured into a hipGraph.  Refused (SVI_ERR_INVALID, with a message): a model without
+ * enable_multitalk; a slot that is not staged, or staged for another frame count than T / patch_t; audio armed through svi_dit_set_audio; NULL or
+ * overlapping outputs; sizes not divisible by the patch. */
+svi_status svi_dit_audio_slot(svi_dit* h, int32_t slot /* 0 or 1 */, const void* audio_first, const void* audio_latter, int32_t n_latter,
+                              svi_stream stream);
+svi_status svi_dit_forward_talk3(svi_dit* h, const void* x, const float* timestep, const void* context_cond, const void* context_uncond,
+                                 const void* clip_feature, const void* y, const void* add_condition, void* out_cond, void* out_uncond,
+                                 void* out_drop_text, int32_t T, int32_t H, int32_t W, int32_t Lc, svi_stream stream);
 
 /* TeaCache support (pipelines/svi_video.py:23-72 class TeaCache, :117-131 its use inside model_fn_wan_video).
  * svi_dit_time_mod: t_mod bf16 [B, 6, dim], the tensor TeaCache.check() compares between steps (host logic decides).

@@ -84,6 +84,19 @@ struct CtxEntry {
 
 struct CtxKV { bf16 *CK, *CVT, *CKi, *CVTi; bool compute; const int* tail; int key_blocks; };
 
+// Talk variant: one clip's audio, projected ONCE (svi_dit_audio_slot): AudioProjModel's tokens AUD [f * 32, 768] and every block's audio cross-attention
+// K [f * 32, dim] / V^T [dim, ld] (audio_cross_attn.kv_linear).  They depend on (audio, weights) only; svi_dit_forward_talk3 reads them where a
+// forward armed through svi_dit_set_audio re-projects them.  The slot owns its buffers: the caller's windows are read while it is staged, never later.
+struct AudSlot {
+    char* base = nullptr;
+    int frames = 0;                 // latent frames the allocation is laid out for
+    bool staged = false;            // false after a weight was bound: the projections were made with the old values
+    int ld = 0;
+    bf16 *H0 = nullptr, *H1 = nullptr, *P3 = nullptr, *AUD = nullptr;
+    std::vector<bf16*> K, VT;
+};
+struct AudKV { const bf16* K; const bf16* VT; int ld; };      // one block's projected audio keys / values of a staged slot
+
 struct svi_dit {
     svi_dit_config cfg;
     int device = -1;                  // claimed by the first compute call (svi_claim_device)
@@ -121,6 +134,7 @@ struct svi_dit {
     int aud_frames = 0;
     bf16 *AH0 = nullptr, *AH1 = nullptr, *AP3 = nullptr, *AUD = nullptr, *AK = nullptr, *AVT = nullptr;
     int ldavt = 0;
+    AudSlot aud_slot[2];              // svi_dit_audio_slot: 0 = the clip's audio, 1 = the null audio (svi_dit_forward_talk3)
     // sequence-parallel shard in flight (svi_dit_sp_begin .. svi_dit_sp_head)
     int sp_rows = 0, sp_row0 = 0, sp_Lc = 0;
     int sp_nb = 1;                    // 2: the shard carries both CFG branches stacked (svi_dit_sp_begin_pair): X = [cond rows | uncond rows]
@@ -270,6 +284,8 @@ extern "C" svi_status svi_dit_destroy(svi_dit* h) {
     if (!h) return SVI_OK;
     if (h->ws.base) (void)hipFree(h->ws.base);
     if (h->aud_base) (void)hipFree(h->aud_base);
+    for (auto& s : h->aud_slot)
+        if (s.base) (void)hipFree(s.base);
     if (h->rope_dev) (void)hipFree(h->rope_dev);
     for (auto& e : h->ctx_entries)
         if (e.base) (void)hipFree(e.base);
@@ -290,6 +306,7 @@ extern "C" svi_status svi_dit_bind_weight(svi_dit* h, const char* name, const vo
     SVI_REQUIRE(((uintptr_t)dev_ptr % 16) == 0, "parameter '%s' is not 16-byte aligned", name);
     *it->second.ptr = reinterpret_cast<const bf16*>(dev_ptr);
     for (auto& e : h->ctx_entries) e.filled = false;      // cached projections were made with the old weights
+    for (auto& s : h->aud_slot) s.staged = false;         // and so were the audio slots'
     ++h->generation;
     return SVI_OK;
 }
@@ -658,9 +675,11 @@ static svi_status fill_block_kv(svi_dit* h, int layer, const bf16* CTX, int Lc, 
 // nb > 1: X holds nb samples stacked (nb * L rows); sample s attends to its own context (CTXs[s], kvs[s]) — the conditional and the
 // unconditional prompt of a CFG step.  Row-local work (norms, projections, MLP) runs once over all rows.
 // audio_frames > 0 (talk variant): X holds rows [audio_row0, audio_row0 + L) of a sequence of audio_frames frames of audio_rpf rows each (one rank: 0, L / f).
-static svi_status block_audio(svi_dit* h, int layer, bf16* X, int L, int f, int row0, int rpf, hipStream_t st);
+// aud_kv (svi_dit_forward_talk3): the block's audio K / V^T of a staged slot, read instead of being projected.
+static svi_status block_audio(svi_dit* h, int layer, bf16* X, int L, int f, int row0, int rpf, hipStream_t st, const AudKV* slot);
 static svi_status run_block_rest_n(svi_dit* h, int layer, bf16* X, const bf16* const* CTXs, const float* modf, int L, int Lc,
-                                   const CtxKV* kvs, int nb, hipStream_t st, int audio_frames = 0, int audio_row0 = 0, int audio_rpf = 0) {
+                                   const CtxKV* kvs, int nb, hipStream_t st, int audio_frames = 0, int audio_row0 = 0, int audio_rpf = 0,
+                                   const AudKV* aud_kv = nullptr) {
     const svi_dit_config& c = h->cfg;
     const BlockW& b = h->blocks[layer];
     Workspace& w = h->ws;
@@ -708,7 +727,7 @@ static svi_status run_block_rest_n(svi_dit* h, int layer, bf16* X, const bf16* c
     if (proj_mx8_on(h)) { SviProfScope _p(PROF_GEMM_CROSS, st); SVI_TRY(linear_mx8(h, w.Hb, true, b.proj_8[5], b.ca.o.b, X, D, R, SVI_EPI_BIAS_GATE_RES, st, nullptr, X, D)); }
     else { SviProfScope _p(PROF_GEMM_CROSS, st); SVI_TRY(linear(w.Hb, D, b.ca.o, X, D, R, D, D, SVI_EPI_BIAS_GATE_RES, st, nullptr, X, D, nb)); }
     // --- talk variant: audio cross-attention between the text cross-attention and the MLP (dit:361-366)
-    if (audio_frames > 0) SVI_TRY(block_audio(h, layer, X, L, audio_frames, audio_row0, audio_rpf, st));
+    if (audio_frames > 0) SVI_TRY(block_audio(h, layer, X, L, audio_frames, audio_row0, audio_rpf, st, aud_kv));
     // --- MLP: x += gate_mlp * W2 gelu_tanh(W1 modulate(norm2 x))                  dit:372-373,334-335
     { SviProfScope _p(PROF_LN, st); SVI_TRY(svi_launch_ln_mod(X, D, w.Hb, D, R, D, c.eps, nullptr, nullptr, sh_m, sc_m, st)); }
     if (h->ffn_mx8) {          // opt-in MX-fp8 MLP: both GEMMs on v_mfma_scale_f32_32x32x64_f8f6f4, activations quantised per 32-element K block
@@ -750,14 +769,15 @@ static svi_status run_block_rest_n(svi_dit* h, int layer, bf16* X, const bf16* c
     return SVI_OK;
 }
 static svi_status run_block_rest(svi_dit* h, int layer, bf16* X, const bf16* CTX, const float* modf, int L, int Lc,
-                                 const CtxKV& kv, hipStream_t st, int audio_frames = 0, int audio_row0 = 0, int audio_rpf = 0) {
-    return run_block_rest_n(h, layer, X, &CTX, modf, L, Lc, &kv, 1, st, audio_frames, audio_row0, audio_rpf);
+                                 const CtxKV& kv, hipStream_t st, int audio_frames = 0, int audio_row0 = 0, int audio_rpf = 0,
+                                 const AudKV* aud_kv = nullptr) {
+    return run_block_rest_n(h, layer, X, &CTX, modf, L, Lc, &kv, 1, st, audio_frames, audio_row0, audio_rpf, aud_kv);
 }
 
 static svi_status run_block(svi_dit* h, int layer, bf16* X, const bf16* CTX, const float* modf, int L, int Lc,
-                            const CtxKV& kv, hipStream_t st, int audio_frames = 0) {
+                            const CtxKV& kv, hipStream_t st, int audio_frames = 0, const AudKV* aud_kv = nullptr) {
     SVI_TRY(run_block_self(h, layer, X, modf, L, st));
-    return run_block_rest(h, layer, X, CTX, modf, L, Lc, kv, st, audio_frames, 0, audio_frames ? L / audio_frames : 0);
+    return run_block_rest(h, layer, X, CTX, modf, L, Lc, kv, st, audio_frames, 0, audio_frames ? L / audio_frames : 0, aud_kv);
 }
 
 // ---- talk variant ---------------------------------------------------------------------------------------------------------------
@@ -782,35 +802,48 @@ static svi_status ensure_audio(svi_dit* h, int f) {
     return SVI_OK;
 }
 // audio_embed = audio_proj(first, latter) (AudioProjModel.forward, dit:82-115) -> AUD bf16 [f * 32, 768]: 32 context tokens per frame
+// H0, H1 [f, 512], P3 [f * 32, 768]: scratch of the projection (the armed forward's own, or a slot's)
+static svi_status project_audio(svi_dit* h, const bf16* first, const bf16* latter, int f, bf16* H0, bf16* H1, bf16* P3, bf16* AUD, hipStream_t st) {
+    const int k0 = 5 * 12 * SVI_AUD_DIM, k1 = 8 * 12 * SVI_AUD_DIM;
+    SVI_TRY(linear(first, k0, h->ap1, H0, 512, 1, 512, k0, SVI_EPI_BIAS_RELU, st));                       // relu(proj1), frame 0
+    if (f > 1) SVI_TRY(linear(latter, k1, h->ap1vf, H0 + 512, 512, f - 1, 512, k1, SVI_EPI_BIAS_RELU, st));   // relu(proj1_vf), frames 1..
+    SVI_TRY(linear(H0, 512, h->ap2, H1, 512, f, 512, 512, SVI_EPI_BIAS_RELU, st));                          // relu(proj2)
+    SVI_TRY(linear(H1, 512, h->ap3, P3, SVI_AUD_TOK * SVI_AUD_DIM, f, SVI_AUD_TOK * SVI_AUD_DIM, 512, SVI_EPI_BIAS, st));   // proj3 -> [f, 32*768]
+    // nn.LayerNorm(768) (eps 1e-5) over every context token
+    return svi_launch_ln_mod(P3, SVI_AUD_DIM, AUD, SVI_AUD_DIM, f * SVI_AUD_TOK, SVI_AUD_DIM, 1e-5f, h->ap_norm_w, h->ap_norm_b, nullptr, nullptr, st);
+}
 static svi_status stage_audio(svi_dit* h, int f, hipStream_t st) {
     SVI_REQUIRE(h->cfg.enable_multitalk, "audio was set on a model without enable_multitalk");
     SVI_REQUIRE(h->aud_latter_n == f - 1, "audio windows cover %d latent frames, the latents have %d", h->aud_latter_n + 1, f);
     SVI_TRY(ensure_audio(h, f));
-    const int k0 = 5 * 12 * SVI_AUD_DIM, k1 = 8 * 12 * SVI_AUD_DIM;
-    SVI_TRY(linear(h->aud_first, k0, h->ap1, h->AH0, 512, 1, 512, k0, SVI_EPI_BIAS_RELU, st));                       // relu(proj1), frame 0
-    if (f > 1) SVI_TRY(linear(h->aud_latter, k1, h->ap1vf, h->AH0 + 512, 512, f - 1, 512, k1, SVI_EPI_BIAS_RELU, st));   // relu(proj1_vf), frames 1..
-    SVI_TRY(linear(h->AH0, 512, h->ap2, h->AH1, 512, f, 512, 512, SVI_EPI_BIAS_RELU, st));                          // relu(proj2)
-    SVI_TRY(linear(h->AH1, 512, h->ap3, h->AP3, SVI_AUD_TOK * SVI_AUD_DIM, f, SVI_AUD_TOK * SVI_AUD_DIM, 512, SVI_EPI_BIAS, st));   // proj3 -> [f, 32*768]
-    // nn.LayerNorm(768) (eps 1e-5) over every context token
-    return svi_launch_ln_mod(h->AP3, SVI_AUD_DIM, h->AUD, SVI_AUD_DIM, f * SVI_AUD_TOK, SVI_AUD_DIM, 1e-5f, h->ap_norm_w, h->ap_norm_b, nullptr, nullptr, st);
+    return project_audio(h, h->aud_first, h->aud_latter, f, h->AH0, h->AH1, h->AP3, h->AUD, st);
+}
+// Block `layer`'s audio K / V^T (audio_cross_attn.kv_linear: rows [0, D) = K, [D, 2D) = V) of the projected tokens AUD [na, 768]: what an armed forward
+// makes per block and a slot keeps per layer — the same two launches, the same bits.
+static svi_status fill_block_audio_kv(svi_dit* h, int layer, const bf16* AUD, int na, bf16* K, bf16* VT, int ld, hipStream_t st) {
+    const BlockW& b = h->blocks[layer];
+    const int D = h->cfg.dim;
+    const Lin lk{b.aud_kv.w, b.aud_kv.b}, lv{b.aud_kv.w + (size_t)D * SVI_AUD_DIM, b.aud_kv.b + D};
+    SVI_TRY(linear(AUD, SVI_AUD_DIM, lk, K, D, na, D, SVI_AUD_DIM, SVI_EPI_BIAS, st));
+    return linear_transposed(AUD, SVI_AUD_DIM, lv, VT, ld, na, D, SVI_AUD_DIM, st);
 }
 // x += proj(attention_per_frame(q_linear(norm_x(x)), kv_linear(audio)))   (DiTBlock.forward dit:361-366; SingleStreamAttention.forward,
 // models/attention.py:318-371 with human_num == 1): frame fr's h*w tokens attend to that frame's 32 audio tokens, scale head_dim^-0.5,
-// no q/k norm, no RoPE.  K | V of the audio tokens depend on (audio, weights) only; they are re-projected per forward (3 GFLOP per block).
+// no q/k norm, no RoPE.  K | V of the audio tokens depend on (audio, weights) only: a forward armed through svi_dit_set_audio re-projects them
+// (3 GFLOP per block), svi_dit_forward_talk3 reads the ones its slot holds (`slot`).
 // X holds rows [row0, row0 + L) of the f * rpf-row sequence (a sequence-parallel shard cuts frames anywhere); K | V cover all f frames, so one
 // frame-segmented attention launch serves any range with the bits of one launch per frame.
-static svi_status block_audio(svi_dit* h, int layer, bf16* X, int L, int f, int row0, int rpf, hipStream_t st) {
+static svi_status block_audio(svi_dit* h, int layer, bf16* X, int L, int f, int row0, int rpf, hipStream_t st, const AudKV* slot) {
     const svi_dit_config& c = h->cfg;
     const BlockW& b = h->blocks[layer];
     Workspace& w = h->ws;
     const int D = c.dim, na = f * SVI_AUD_TOK;
     SVI_REQUIRE(rpf > 0 && row0 >= 0 && (long)row0 + L <= (long)f * rpf, "audio attention: rows [%d, %d) outside %d frames of %d rows", row0, row0 + L, f, rpf);
-    const Lin lk{b.aud_kv.w, b.aud_kv.b}, lv{b.aud_kv.w + (size_t)D * SVI_AUD_DIM, b.aud_kv.b + D};      // kv_linear rows [0, D) = K, [D, 2D) = V
     SVI_TRY(svi_launch_ln_mod(X, D, w.Hb, D, L, D, c.eps, b.normx_w, b.normx_b, nullptr, nullptr, st));
     SVI_TRY(linear(w.Hb, D, b.aud_q, w.QK, 2 * D, L, D, D, SVI_EPI_BIAS, st));
-    SVI_TRY(linear(h->AUD, SVI_AUD_DIM, lk, h->AK, D, na, D, SVI_AUD_DIM, SVI_EPI_BIAS, st));
-    SVI_TRY(linear_transposed(h->AUD, SVI_AUD_DIM, lv, h->AVT, h->ldavt, na, D, SVI_AUD_DIM, st));
-    SVI_TRY(svi_launch_flash_frames(w.QK, 2 * D, h->AK, D, h->AVT, h->ldavt, w.Hb, D, row0, L, rpf, SVI_AUD_TOK, c.num_heads, st));
+    if (!slot) SVI_TRY(fill_block_audio_kv(h, layer, h->AUD, na, h->AK, h->AVT, h->ldavt, st));
+    const AudKV kv = slot ? *slot : AudKV{h->AK, h->AVT, h->ldavt};
+    SVI_TRY(svi_launch_flash_frames(w.QK, 2 * D, kv.K, D, kv.VT, kv.ld, w.Hb, D, row0, L, rpf, SVI_AUD_TOK, c.num_heads, st));
     return linear(w.Hb, D, b.aud_proj, X, D, L, D, D, SVI_EPI_BIAS_GATE_RES, st, nullptr, X, D);
 }
 
@@ -1136,6 +1169,139 @@ extern "C" svi_status svi_dit_set_audio(svi_dit* h, const void* audio_first, con
     return SVI_OK;
 }
 
+// One clip's audio windows -> a slot: AudioProjModel once, then every block's audio K / V^T (include/svi_hip.h).  A slot that holds this frame count is
+// rewritten where it stands (the clip boundary of a resident loop: no address and no generation moves); otherwise it is (re)allocated.
+extern "C" svi_status svi_dit_audio_slot(svi_dit* h, int32_t slot, const void* audio_first, const void* audio_latter, int32_t n_latter, svi_stream stream) {
+    SVI_REQUIRE(h, "null handle");
+    SVI_REQUIRE(slot == 0 || slot == 1, "svi_dit_audio_slot: slot %d (0 = the clip's audio, 1 = the null audio)", slot);
+    AudSlot& s = h->aud_slot[slot];
+    if (!audio_first) {
+        if (s.base) { SVI_CHECK_HIP(hipFree(s.base)); s = AudSlot{}; ++h->generation; }
+        return SVI_OK;
+    }
+    SVI_REQUIRE_DEVICE(h);
+    SVI_REQUIRE(h->cfg.enable_multitalk, "svi_dit_audio_slot: the model was created without enable_multitalk");
+    SVI_REQUIRE(n_latter >= 0 && (n_latter == 0 || audio_latter), "svi_dit_audio_slot: %d later frames but no audio_latter", n_latter);
+    SVI_REQUIRE(((uintptr_t)audio_first % 16) == 0 && ((uintptr_t)audio_latter % 16) == 0, "svi_dit_audio_slot: audio windows must be 16-byte aligned");
+    SVI_TRY(svi_dit_check_bound(h));
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int f = n_latter + 1, nl = h->cfg.num_layers;
+    const size_t D = h->cfg.dim, na = (size_t)f * SVI_AUD_TOK;
+    if (!s.base || s.frames != f) {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) {
+            svi_set_error("svi_dit_audio_slot: slot %d must be allocated while the stream is being captured: stage this frame count once before the capture", slot);
+            return SVI_ERR_INVALID;
+        }
+        (void)hipGetLastError();
+        const int ld = (int)((na + 7) / 8 * 8);
+        size_t off = 0;
+        auto take = [&](size_t bytes) { size_t o = off; off += al(bytes); return o; };
+        const size_t oh0 = take((size_t)f * 512 * 2), oh1 = take((size_t)f * 512 * 2), op3 = take(na * SVI_AUD_DIM * 2), oaud = take(na * SVI_AUD_DIM * 2);
+        std::vector<size_t> ok(nl), ov(nl);
+        for (int l = 0; l < nl; ++l) { ok[l] = take(na * D * 2); ov[l] = take(D * ld * 2); }
+        if (s.base) { SVI_CHECK_HIP(hipFree(s.base)); s = AudSlot{}; }
+        char* base = nullptr;
+        hipError_t e = hipMalloc((void**)&base, off);
+        if (e != hipSuccess) { svi_set_error("hipMalloc(%zu B audio slot %d) failed: %s", off, slot, hipGetErrorString(e)); return SVI_ERR_OOM; }
+        s.base = base; s.frames = f; s.ld = ld;
+        SVI_CHECK_HIP(hipMemsetAsync(base, 0, off, st));
+        auto P = [&](size_t o) { return reinterpret_cast<bf16*>(base + o); };
+        s.H0 = P(oh0); s.H1 = P(oh1); s.P3 = P(op3); s.AUD = P(oaud);
+        s.K.resize(nl); s.VT.resize(nl);
+        for (int l = 0; l < nl; ++l) { s.K[l] = P(ok[l]); s.VT[l] = P(ov[l]); }
+        ++h->generation;
+    } else if (!s.staged) ++h->generation;          // dropped by a re-bind: staged anew (the buffers are reused; a graph made before the re-bind is stale anyway)
+    s.staged = false;
+    SVI_TRY(project_audio(h, reinterpret_cast<const bf16*>(audio_first), reinterpret_cast<const bf16*>(audio_latter), f, s.H0, s.H1, s.P3, s.AUD, st));
+    for (int l = 0; l < nl; ++l) SVI_TRY(fill_block_audio_kv(h, l, s.AUD, (int)na, s.K[l], s.VT[l], s.ld, st));
+    s.staged = true;
+    return SVI_OK;
+}
+
+// The three forwards of a talk step (svi_video_talk.py:455-458) in one call: cond (prompt, audio, add_condition), uncond (negative prompt, null audio,
+// no add_condition), drop-text (negative prompt, audio, add_condition).  They see the same latents and timestep: the timestep embedding and the
+// modulation rows, patchify and the patch embedding are computed once, block 0's self-attention third once per distinct embedded input (one run without
+// add_condition; two with it, cond and drop-text sharing), and every block's audio K / V^T come from the staged slots.  The branches then run one after
+// another on the L-row workspace (forward_pair's unstacked form); X2 holds what the next branch starts from.  With add_condition the unconditional
+// branch goes first, so that ONE snapshot buffer serves: the plain patch embedding until the conditioned rows are formed from it, then the conditioned
+// rows behind block 0's self-attention.  The outputs do not depend on the order.  Same kernels on the same operands as three armed svi_dit_forward calls.
+static svi_status forward_talk3(svi_dit* h, const bf16* x, const float* timestep, const bf16* ctx_c, const bf16* ctx_u, const bf16* clip, const bf16* y,
+                                const bf16* addc, bf16* out_c, bf16* out_u, bf16* out_d, int T, int H, int W, int Lc, hipStream_t st) {
+    const svi_dit_config& c = h->cfg;
+    const int D = c.dim;
+    const int f = T / c.patch_t, hh = H / c.patch_h, ww = W / c.patch_w;
+    const int L = f * hh * ww;
+    SVI_TRY(ensure_workspace(h, L, Lc, st));
+    SVI_TRY(ensure_rope(h, f, hh, ww));
+    Workspace& w = h->ws;
+    SVI_TRY(stage_time(h, timestep, st));
+    SVI_TRY(stage_embed(h, x, y, nullptr, T, H, W, L, st));
+    const size_t xbytes = (size_t)L * D * 2;
+    auto branch = [&](const bf16* ctx, int slot, bf16* out) -> svi_status {          // X: the branch's rows behind block 0's self-attention
+        const AudSlot& s = h->aud_slot[slot];
+        CtxUse cu{};
+        SVI_TRY(stage_context(h, ctx, clip, y, Lc, &cu, st));      // (scratch rows of its own: X is untouched)
+        for (int l = 0; l < c.num_layers; ++l) {
+            const AudKV akv{s.K[l], s.VT[l], s.ld};
+            const float* modf = w.modf + (size_t)l * 6 * D;
+            if (l) SVI_TRY(run_block_self(h, l, w.X, modf, L, st));
+            SVI_TRY(run_block_rest(h, l, w.X, cu.CTXp, modf, L, Lc, kv_of(h, cu, l), st, f, 0, hh * ww, &akv));
+        }
+        return stage_head(h, out, T, H, W, L, st);
+    };
+    if (addc) {
+        SVI_CHECK_HIP(hipMemcpyAsync(w.X2, w.X, xbytes, hipMemcpyDeviceToDevice, st));
+        SVI_TRY(run_block_self(h, 0, w.X, w.modf, L, st));
+        SVI_TRY(branch(ctx_u, 1, out_u));
+        SVI_CHECK_HIP(hipMemcpyAsync(w.X, w.X2, xbytes, hipMemcpyDeviceToDevice, st));
+        SVI_TRY(svi_launch_add_bf16(w.X, addc, (int64_t)L * D, st));
+        SVI_TRY(run_block_self(h, 0, w.X, w.modf, L, st));
+        SVI_CHECK_HIP(hipMemcpyAsync(w.X2, w.X, xbytes, hipMemcpyDeviceToDevice, st));
+        SVI_TRY(branch(ctx_c, 0, out_c));
+        SVI_CHECK_HIP(hipMemcpyAsync(w.X, w.X2, xbytes, hipMemcpyDeviceToDevice, st));
+        return branch(ctx_u, 0, out_d);
+    }
+    SVI_TRY(run_block_self(h, 0, w.X, w.modf, L, st));
+    SVI_CHECK_HIP(hipMemcpyAsync(w.X2, w.X, xbytes, hipMemcpyDeviceToDevice, st));
+    SVI_TRY(branch(ctx_c, 0, out_c));
+    SVI_CHECK_HIP(hipMemcpyAsync(w.X, w.X2, xbytes, hipMemcpyDeviceToDevice, st));
+    SVI_TRY(branch(ctx_u, 1, out_u));
+    SVI_CHECK_HIP(hipMemcpyAsync(w.X, w.X2, xbytes, hipMemcpyDeviceToDevice, st));
+    return branch(ctx_u, 0, out_d);
+}
+
+extern "C" svi_status svi_dit_forward_talk3(svi_dit* h, const void* x, const float* timestep, const void* context_cond, const void* context_uncond,
+                                            const void* clip_feature, const void* y, const void* add_condition, void* out_cond, void* out_uncond,
+                                            void* out_drop_text, int32_t T, int32_t H, int32_t W, int32_t Lc, svi_stream stream) {
+    SVI_REQUIRE(h && x && timestep && context_cond && context_uncond, "svi_dit_forward_talk3: null argument");
+    SVI_REQUIRE(out_cond && out_uncond && out_drop_text, "svi_dit_forward_talk3: null output");
+    SVI_REQUIRE_DEVICE(h);
+    const svi_dit_config& c = h->cfg;
+    SVI_REQUIRE(c.enable_multitalk, "svi_dit_forward_talk3: the model was created without enable_multitalk");
+    SVI_REQUIRE(!h->aud_first, "svi_dit_forward_talk3: audio is armed through svi_dit_set_audio; disarm it (the three branches read the slots of svi_dit_audio_slot)");
+    SVI_REQUIRE(T > 0 && H > 0 && W > 0 && Lc > 0, "svi_dit_forward_talk3: bad sizes");
+    SVI_REQUIRE(T % c.patch_t == 0 && H % c.patch_h == 0 && W % c.patch_w == 0, "latent size %dx%dx%d is not divisible by the patch size", T, H, W);
+    const size_t obytes = (size_t)c.out_dim * T * H * W * 2;
+    const uintptr_t o[3] = {(uintptr_t)out_cond, (uintptr_t)out_uncond, (uintptr_t)out_drop_text};
+    for (int i = 0; i < 3; ++i)
+        for (int j = i + 1; j < 3; ++j)
+            SVI_REQUIRE(o[i] + obytes <= o[j] || o[j] + obytes <= o[i], "svi_dit_forward_talk3: aliased outputs (each branch needs a buffer of its own)");
+    SVI_REQUIRE(y || c.in_dim == 16, "this model takes %d extra input channels: y must be given", c.in_dim - 16);
+    SVI_REQUIRE(!c.has_image_input || clip_feature, "has_image_input model needs clip_feature");
+    const int f = T / c.patch_t;
+    for (int s = 0; s < 2; ++s) {
+        const AudSlot& a = h->aud_slot[s];
+        SVI_REQUIRE(a.base && a.staged, "svi_dit_forward_talk3: audio slot %d is not staged (svi_dit_audio_slot)", s);
+        SVI_REQUIRE(a.frames == f, "svi_dit_forward_talk3: audio slot %d covers %d latent frames, the latents have %d", s, a.frames, f);
+    }
+    SVI_TRY(svi_dit_check_bound(h));
+    return forward_talk3(h, reinterpret_cast<const bf16*>(x), timestep, reinterpret_cast<const bf16*>(context_cond), reinterpret_cast<const bf16*>(context_uncond),
+                         reinterpret_cast<const bf16*>(clip_feature), reinterpret_cast<const bf16*>(y), reinterpret_cast<const bf16*>(add_condition),
+                         reinterpret_cast<bf16*>(out_cond), reinterpret_cast<bf16*>(out_uncond), reinterpret_cast<bf16*>(out_drop_text), T, H, W, Lc,
+                         reinterpret_cast<hipStream_t>(stream));
+}
+
 extern "C" svi_status svi_dit_forward(svi_dit* h, const void* x, const float* timestep, const void* context,
                                       const void* clip_feature, const void* y, const void* add_condition, void* out,
                                       int32_t B, int32_t T, int32_t H, int32_t W, int32_t Lc, svi_stream stream) {
@@ -1220,7 +1386,7 @@ static svi_status cfg_pair_entry(svi_dit* h, const void* x, const float* timeste
     SVI_REQUIRE(h && x && timestep && context_cond && context_uncond && out_cond && out_uncond, "svi_dit_forward_cfg_pair: null argument");
     SVI_REQUIRE_DEVICE(h);
     SVI_REQUIRE(B > 0 && T > 0 && H > 0 && W > 0 && Lc > 0, "svi_dit_forward_cfg_pair: bad sizes");
-    if (h->aud_first) { svi_set_error("svi_dit_forward_cfg_pair: the talk variant's branches differ in their audio; run them as separate forwards"); return SVI_ERR_UNSUPPORTED; }
+    if (h->aud_first) { svi_set_error("svi_dit_forward_cfg_pair: the talk variant's branches differ in their audio; the three guidance forwards of a talk step are one call of their own (svi_dit_forward_talk3)"); return SVI_ERR_UNSUPPORTED; }
     SVI_REQUIRE(y || h->cfg.in_dim == 16, "this model takes %d extra input channels: y must be given", h->cfg.in_dim - 16);
     SVI_REQUIRE(!h->cfg.has_image_input || clip_feature, "has_image_input model needs clip_feature");
     SVI_REQUIRE(tea_mode >= 0 && tea_mode <= 2 && (tea_mode == 0 || (residual_cond && residual_uncond && residual_cond != residual_uncond)),
@@ -1352,7 +1518,7 @@ extern "C" svi_status svi_dit_sp_begin_pair(svi_dit* h, const void* x, const flo
     const svi_dit_config& c = h->cfg;
     SVI_REQUIRE(h->ctx_cache_on, "svi_dit_sp_begin_pair: the stacked CFG pair needs the context cache (svi_dit_context_cache(h, 1))");
     SVI_REQUIRE(T > 0 && H > 0 && W > 0 && Lc > 0 && T % c.patch_t == 0 && H % c.patch_h == 0 && W % c.patch_w == 0, "svi_dit_sp_begin_pair: bad sizes");
-    if (h->aud_first) { svi_set_error("svi_dit_sp_begin_pair: the talk variant's branches differ in their audio; run them as separate shard forwards (svi_dit_sp_begin)"); return SVI_ERR_UNSUPPORTED; }
+    if (h->aud_first) { svi_set_error("svi_dit_sp_begin_pair: the talk variant's branches differ in their audio; run them as separate shard forwards (svi_dit_sp_begin) — on one rank svi_dit_forward_talk3 serves the step"); return SVI_ERR_UNSUPPORTED; }
     SVI_REQUIRE(y || c.in_dim == 16, "this model takes %d extra input channels: y must be given", c.in_dim - 16);
     SVI_REQUIRE(!c.has_image_input || clip_feature, "has_image_input model needs clip_feature");
     const int f = T / c.patch_t, hh = H / c.patch_h, ww = W / c.patch_w, L = f * hh * ww;

@@ -86,6 +86,7 @@ class WanDiT:
         self.num_heads, self.num_layers, self.has_image_input = num_heads, num_layers, bool(has_image_input)
         self.enable_multitalk = bool(enable_multitalk)
         self._audio = None                  # the armed audio windows (kept alive: the C side borrows their pointers)
+        self._audio_slots: Dict[int, int] = {}       # stage_audio: slot -> latent frames it is staged for (a re-bind drops both)
         cfg = L.DitConfig(dim, in_dim, ffn_dim, out_dim, text_dim, freq_dim, eps, *self.patch_size, num_heads,
                           num_layers, int(self.has_image_input), int(self.enable_multitalk))
         h = C.c_void_p()
@@ -155,6 +156,7 @@ class WanDiT:
             L.check(lib.svi_dit_bind_weight(self._h, name.encode(), t.data_ptr(), L.SVI_BF16, shape, t.dim()),
                     f"bind {name}")
             self._params[name] = t
+        self._audio_slots = {}              # svi_dit_bind_weight drops the audio slots: their projections were made with the old weights
         L.check(lib.svi_dit_check_bound(self._h), "svi_dit_check_bound")
         # what weights_changed() watches: the bound bf16 tensors and, in FP8 storage mode, the e4m3 tensors they were cast from
         self._param_versions = [(t, _version(t)) for t in self._params.values()] + [(t, _version(t)) for t in self._fp8_sources.values()]
@@ -359,15 +361,39 @@ class WanDiT:
             L.check(L.lib().svi_dit_set_audio(self._h, None, None, 0), "svi_dit_set_audio")
             self._audio = None
             return
+        a0, a1 = self._audio_windows(audio_embed_tuple)
+        L.check(L.lib().svi_dit_set_audio(self._h, L.ptr(a0), L.ptr(a1) if a1.shape[1] else None, a1.shape[1]), "svi_dit_set_audio")
+        self._audio = (a0, a1)
+
+    def _audio_windows(self, audio_embed_tuple):
+        """The two audio windows of a clip, checked, as contiguous CUDA bf16 (set_audio, stage_audio)."""
         if not self.enable_multitalk:
             raise ValueError("audio_embed_tuple was given to a model without enable_multitalk")
         a0, a1 = audio_embed_tuple
         if tuple(a0.shape) != (1, 1, 5, 12, 768) or a1.dim() != 5 or tuple(a1.shape[:1] + a1.shape[2:]) != (1, 8, 12, 768):
             raise ValueError(f"audio_embed_tuple must be ([1,1,5,12,768], [1,T-1,8,12,768]) (got {tuple(a0.shape)}, {tuple(a1.shape)})")
-        a0 = a0.to(device="cuda", dtype=torch.bfloat16).contiguous()
-        a1 = a1.to(device="cuda", dtype=torch.bfloat16).contiguous()
-        L.check(L.lib().svi_dit_set_audio(self._h, L.ptr(a0), L.ptr(a1) if a1.shape[1] else None, a1.shape[1]), "svi_dit_set_audio")
-        self._audio = (a0, a1)
+        return a0.to(device="cuda", dtype=torch.bfloat16).contiguous(), a1.to(device="cuda", dtype=torch.bfloat16).contiguous()
+
+    def stage_audio(self, slot: int, audio_embed_tuple) -> None:
+        """Project one clip's audio windows into audio slot `slot` (0: the clip's audio, 1: the null audio) for forward_talk3: AudioProjModel and every
+        block's audio K / V^T, once (svi_dit_audio_slot).  The slot owns the results — the tensors given here are read by this call's work on the current
+        stream and may be rewritten afterwards.  Staging a slot again for the same number of latent frames rewrites it in place (generation() does not
+        move: a captured step stays valid — the clip boundary of a resident loop); another frame count re-allocates; None frees the slot."""
+        if slot not in (0, 1):
+            raise ValueError(f"stage_audio: slot must be 0 (the clip's audio) or 1 (the null audio), got {slot!r}")
+        if audio_embed_tuple is None:
+            L.check(L.lib().svi_dit_audio_slot(self._h, slot, None, None, 0, L.current_stream()), "svi_dit_audio_slot")
+            self._audio_slots.pop(slot, None)
+            return
+        a0, a1 = self._audio_windows(audio_embed_tuple)
+        self._refresh_if_weights_changed()
+        L.check(L.lib().svi_dit_audio_slot(self._h, slot, L.ptr(a0), L.ptr(a1) if a1.shape[1] else None, a1.shape[1], L.current_stream()),
+                "svi_dit_audio_slot")
+        self._audio_slots[slot] = a1.shape[1] + 1
+
+    def audio_staged(self, frames: int) -> bool:
+        """Both audio slots hold projections made with the bound weights for `frames` latent frames."""
+        return self._audio_slots.get(0) == frames and self._audio_slots.get(1) == frames
 
     def tokens(self, T: int, H: int, W: int) -> int:
         pt, ph, pw = self.patch_size
@@ -426,6 +452,47 @@ class WanDiT:
                                                  L.ptr(clip_feature), L.ptr(y), L.ptr(add_condition), L.ptr(out_cond), L.ptr(out_uncond),
                                                  B, T, H, W, context_cond.shape[1], L.current_stream()), "svi_dit_forward_cfg_pair")
         return out_cond, out_uncond
+
+    def forward_talk3(self, x: torch.Tensor, timestep: torch.Tensor, context_cond: torch.Tensor, context_uncond: torch.Tensor,
+                      clip_feature: Optional[torch.Tensor] = None, y: Optional[torch.Tensor] = None, add_condition: Optional[torch.Tensor] = None,
+                      out_cond: Optional[torch.Tensor] = None, out_uncond: Optional[torch.Tensor] = None, out_drop_text: Optional[torch.Tensor] = None):
+        """The three guidance forwards of a talk step (SVITalkVideoPipeline._sample_with_multitalk, svi_video_talk.py:455-458) in one call
+        (svi_dit_forward_talk3): conditional (context_cond, audio slot 0, add_condition), unconditional (context_uncond, audio slot 1 — the null
+        audio —, no add_condition), drop-text (context_uncond, audio slot 0, add_condition).  The audio comes from the slots (stage_audio) — nothing
+        may be armed through set_audio.  What the branches share is computed once (timestep embedding, patch embedding, block 0's self-attention
+        per distinct embedded input; every block's audio K / V^T were projected when the slots were staged); each output is bit-identical to
+        model_fn_wan_talk_video with that branch's inputs.  One sample per call, as the talk variant's forward."""
+        if not x.is_cuda:
+            raise RuntimeError("svi_hip runs on the GPU only")
+        if context_cond.shape != context_uncond.shape:
+            raise ValueError("the two prompt embeddings of a talk step must have the same shape")
+        self.check_inputs(x, (context_cond, context_uncond), clip_feature, y, add_condition)
+        if x.shape[0] != 1:
+            raise ValueError(f"the talk variant takes one sample per forward (audio windows of one clip), got a batch of {x.shape[0]}")
+        if not self.has_image_input:
+            clip_feature = None
+        x = x.to(torch.bfloat16).contiguous()
+        context_cond, context_uncond, clip_feature = self._prompt_args(context_cond, context_uncond, clip_feature)
+        timestep = timestep.to(device=x.device, dtype=torch.float32).reshape(-1).contiguous()
+        if timestep.numel() != 1:
+            raise ValueError(f"forward_talk3 takes one timestep (got {timestep.numel()})")
+        _, _, T, H, W = x.shape
+        if y is not None:
+            y = y.to(torch.bfloat16).contiguous()
+        if add_condition is not None:
+            add_condition = add_condition.to(torch.bfloat16).contiguous()
+        shape = (1, self.out_dim, T, H, W)
+        outs = []
+        for name, o in (("out_cond", out_cond), ("out_uncond", out_uncond), ("out_drop_text", out_drop_text)):
+            if o is None:
+                o = torch.empty(shape, dtype=torch.bfloat16, device=x.device)
+            elif not o.is_cuda or o.dtype != torch.bfloat16 or not o.is_contiguous() or tuple(o.shape) != shape:
+                raise ValueError(f"{name} must be a contiguous CUDA bf16 tensor of shape {shape} (got {tuple(o.shape)}, {o.dtype}, {o.device})")
+            outs.append(o)
+        L.check(L.lib().svi_dit_forward_talk3(self._h, L.ptr(x), L.ptr(timestep), L.ptr(context_cond), L.ptr(context_uncond), L.ptr(clip_feature),
+                                              L.ptr(y), L.ptr(add_condition), L.ptr(outs[0]), L.ptr(outs[1]), L.ptr(outs[2]), T, H, W,
+                                              context_cond.shape[1], L.current_stream()), "svi_dit_forward_talk3")
+        return tuple(outs)
 
     def block_forward(self, layer: int, x: torch.Tensor, context: torch.Tensor, t_mod: torch.Tensor,
                       grid: Tuple[int, int, int]) -> torch.Tensor:

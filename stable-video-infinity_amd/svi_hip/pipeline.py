@@ -70,12 +70,16 @@ class DenoiseLoop:
         (adopt()).  A clip boundary then moves no address: the prompt's cache entries are recomputed in place (WanDiT.refill_context) and the step
         graph captured for the first clip of a stream is replayed by every later clip of the same shapes — no eager step, no re-capture, no
         re-instantiation per clip.  The context cache stays on while the loop lives (close() turns it off).  Same kernels on the same values:
-        bit-identical to the non-resident loop (tests/test_gpu_stream.py)."""
+        bit-identical to the non-resident loop (tests/test_gpu_stream.py).
+        The talk variant (sample_multitalk) is on the same path: with `graph` on, a step is ONE forward_talk3 call — the three guidance forwards, their
+        shared prefix computed once, the audio K / V^T of every block projected once per clip into the DiT's audio slots — captured on the clip's first
+        step and replayed; a resident loop re-stages the slots in place at a clip boundary and keeps replaying.  `graph=False` keeps the three eager
+        model_fn_wan_talk_video calls per step.  Bit-identical either way (tests/test_gpu_talk3.py)."""
         self.dit = dit
         self.cfg_pair = cfg_pair
         self.sequence_parallel, self.sp_group = sequence_parallel, sp_group
         self.scheduler = scheduler or FlowMatchScheduler(shift=5, sigma_min=0.0, extra_one_step=True)
-        self._cond = self._uncond = None
+        self._cond = self._uncond = self._drop = None      # the step's noise predictions (the talk step has a third: drop-text)
         if graph and (cfg_pair is not None or sequence_parallel):
             raise ValueError("graph capture covers the single-rank step only")
         self.graph = (cfg_pair is None and not sequence_parallel) if graph is None else bool(graph)
@@ -186,6 +190,8 @@ class DenoiseLoop:
         self._graph = None
         self._tea_graphs.clear()
         self._slots, self._slot_src = {}, {}
+        for slot in list(self.dit._audio_slots):         # a talk stream's audio slots (about 0.55 GB each at the 14B width)
+            self.dit.stage_audio(slot, None)
         if self.resident and self.dit._ctx_cache_on:
             self.dit.context_cache(False)
         self._retire_capture_stream()                    # the stream's end also ends its capture stream and the library's buffers keyed to it
@@ -251,6 +257,12 @@ class DenoiseLoop:
         capturing one mode leaves the other's graph alone."""
         self.dit._refresh_if_weights_changed()          # a LoRA merge since the last step re-binds (and moves the epoch) BEFORE the key is formed
         slot, key, tensors = self._graph_key(latents, ctx_pos, ctx_neg, cfg_scale, split, cond, tea)
+        self._replay_or_capture(slot, key, tensors, latents.device, timestep,
+                                lambda ts: self._forwards(latents, ts, ctx_pos, ctx_neg, cfg_scale, split, cond, ucond, tea))
+
+    def _replay_or_capture(self, slot, key, tensors, device, timestep, run) -> None:
+        """Replay the graph held under `slot` while `key` and the DiT's generation still hold; else run `run(timestep tensor)` eagerly on the loop's
+        capture stream — it IS this step — and record it right behind itself.  See _forwards_graphed for the rules."""
         held = self._graph if slot is None else self._tea_graphs.get(slot)
         stale = held is None or held["key"] != key or held["generation"] != self.dit.generation()
         if stale:
@@ -258,9 +270,9 @@ class DenoiseLoop:
                 self._graph = None
             else:
                 self._tea_graphs.pop(slot, None)
-            if self._capture_stream is None or self._capture_stream.device != latents.device:
+            if self._capture_stream is None or self._capture_stream.device != device:
                 self._retire_capture_stream()
-                self._capture_stream = torch.cuda.Stream(device=latents.device)
+                self._capture_stream = torch.cuda.Stream(device=device)
                 # a loop that is simply dropped (DenoiseLoop(m).step(...)) must not leave the library's per-stream buffers (flag words, split-K
                 # partials, the fp8 attention operands: ~100 MB at the C2 size) keyed to a pool stream for the life of the process
                 self._stream_finalizer = weakref.finalize(self, _release_stream_buffers, self._capture_stream)
@@ -271,13 +283,13 @@ class DenoiseLoop:
             with torch.cuda.stream(side):
                 # this step itself, eagerly: it also sizes the workspaces, fills the context cache and creates the flag words,
                 # so that the recording below allocates nothing
-                self._forwards(latents, ts_static, ctx_pos, ctx_neg, cfg_scale, split, cond, ucond, tea)
+                run(ts_static)
             side.synchronize()
             g = torch.cuda.CUDAGraph()
             # recorded, not executed: self._cond / self._uncond keep the eager step's results.  thread_local: other threads of the process (a
             # communicator's watchdog, a data loader) are not bound by this capture's rules
             with torch.cuda.graph(g, stream=side, capture_error_mode="thread_local"):
-                self._forwards(latents, ts_static, ctx_pos, ctx_neg, cfg_scale, split, cond, ucond, tea)
+                run(ts_static)
             torch.cuda.current_stream().wait_stream(side)
             held = dict(key=key, graph=g, ts=ts_static, pins=tensors, generation=self.dit.generation())
             if slot is None:
@@ -385,8 +397,15 @@ class DenoiseLoop:
         add_condition), unconditional (negative prompt, null audio, no add_condition), drop-text (negative prompt, audio, add_condition) —
         combined as uncond + text*(cond - drop_text) + audio*(drop_text - uncond); one forward when both scales are 1.
         A loop built with sequence_parallel=True (+ sp_group) runs each of the three forwards on this rank's sequence shard
-        (model_fn_wan_talk_video with use_unified_sequence_parallel): every rank ends with the full noise predictions and the same latents."""
+        (model_fn_wan_talk_video with use_unified_sequence_parallel): every rank ends with the full noise predictions and the same latents.
+        A single-rank loop with `graph` on (the default) and three forwards to run takes the one-call step instead (_sample_talk3): same bits."""
         from .dit import model_fn_wan_talk_video
+        if self.graph and self.cfg_pair is None and not self.sequence_parallel and (text_scale != 1.0 or audio_scale != 1.0):
+            self.scheduler.set_timesteps(num_inference_steps, denoising_strength=denoising_strength, shift=sigma_shift)
+            if add_condition is not None:
+                cond = dict(cond, add_condition=add_condition)
+            return self._sample_talk3(latents, ctx_pos, ctx_neg, audio_embed_tuple, audio_embed_tuple_null, text_scale, audio_scale,
+                                      self.scheduler.timesteps, self.scheduler.step_delta, progress_bar_cmd, cond)
         fn = model_fn_wan_talk_video
         if self.sequence_parallel:
             self.dit.sp_group = self.sp_group
@@ -414,6 +433,56 @@ class DenoiseLoop:
         finally:
             self.dit.context_cache(False)
         return latents
+
+    def _talk3_graphed(self, latents, timestep, ctx_pos, ctx_neg, cond) -> None:
+        """The three forwards of one talk step into self._cond / _uncond / _drop: the captured forward_talk3 call replayed, captured on first use
+        (_replay_or_capture, under _forwards_graphed's rules; the key is _graph_key's plus the third output — the audio slots' buffers are the DiT's:
+        its generation() covers them, and a slot rewritten in place for the next clip leaves it alone)."""
+        self.dit._refresh_if_weights_changed()          # (a re-bind drops the audio slots: forward_talk3 then refuses by name — stage them again)
+        _, key, tensors = self._graph_key(latents, ctx_pos, ctx_neg, 0.0, False, cond)
+        d = self._drop
+        key += ("talk3", (d.data_ptr(), tuple(d.shape), d.dtype, _version(d)))
+        self._replay_or_capture(None, key, tensors + [d], latents.device, timestep,
+                                lambda ts: self.dit.forward_talk3(latents, ts, ctx_pos, ctx_neg, out_cond=self._cond, out_uncond=self._uncond,
+                                                                  out_drop_text=self._drop, **cond))
+
+    def _sample_talk3(self, latents, ctx_pos, ctx_neg, audio_embed_tuple, audio_embed_tuple_null, text_scale, audio_scale, timesteps, step_delta,
+                      progress_bar_cmd, cond) -> torch.Tensor:
+        """The talk clip on the graphed path: both audio tuples are projected into the DiT's audio slots once, then every step is one forward_talk3
+        (replayed from the first step's capture) plus the fused three-way guidance + Euler kernel.  `cond`: clip_feature, y, add_condition.  A resident
+        loop copies the clip's inputs into its own tensors (adopt) and re-stages the slots where they stand: the next clip of the same shapes replays."""
+        resident = self.resident
+        dev = latents.device
+        if resident:
+            if not self.dit._ctx_cache_on:
+                self.dit.context_cache(True)
+            latents, ctx_pos, ctx_neg, cond = self.adopt(latents, ctx_pos, ctx_neg, {k: v for k, v in cond.items() if v is not None})
+        else:
+            latents = latents.to(torch.bfloat16).contiguous().clone()
+            ctx_pos = ctx_pos.to(device=dev, dtype=torch.bfloat16).contiguous()
+            ctx_neg = ctx_neg.to(device=dev, dtype=torch.bfloat16).contiguous()
+            # converted once: the captured step reads these very tensors
+            cond = {k: (v.to(device=dev, dtype=torch.bfloat16).contiguous() if isinstance(v, torch.Tensor) else v) for k, v in cond.items() if v is not None}
+            self.dit.context_cache(True)
+        ts_dev = timesteps.to(device=dev, dtype=torch.float32)
+        try:
+            self.dit.stage_audio(0, audio_embed_tuple)
+            self.dit.stage_audio(1, audio_embed_tuple_null)
+            if self._cond is None or self._cond.shape != latents.shape:
+                self._cond = torch.empty_like(latents)
+                self._uncond = torch.empty_like(latents)
+            if self._drop is None or self._drop.shape != latents.shape:
+                self._drop = torch.empty_like(latents)
+            for i, t in enumerate(progress_bar_cmd(timesteps)):
+                self._talk3_graphed(latents, ts_dev[i:i + 1], ctx_pos, ctx_neg, cond)
+                ops.cfg3_step_(latents, self._cond, self._uncond, self._drop, text_scale, audio_scale, step_delta(timesteps[i]))
+        finally:
+            if not resident:
+                self.drop_graph()                 # the graph reads this clip's tensors, cache entries and audio slots: it dies with the clip
+                self.dit.stage_audio(0, None)
+                self.dit.stage_audio(1, None)
+                self.dit.context_cache(False)
+        return latents.clone() if resident else latents
 
     @torch.no_grad()
     def sample(self, latents: torch.Tensor, ctx_pos: torch.Tensor, ctx_neg: Optional[torch.Tensor],
@@ -566,6 +635,44 @@ def _hip_sample_with_regular_video(self, latents, prompt_emb_posi, prompt_emb_ne
     return lat.clone() if resident else lat
 
 
+def _talk_sampler_passes_through(hip, latents, prompt_emb_posi, prompt_emb_nega, image_emb, extra_input, tea_cache_posi, tea_cache_nega, usp_kwargs,
+                                 use_controlnet, cfg_scale) -> bool:
+    """What install()'s talk sampler hands to the pipeline's original `_sample_with_multitalk` (which still reaches the HIP forward through the swapped
+    model_fn_wan_talk_video): TeaCache objects, controlnet, sequence parallelism, extra inputs, prompt / image dicts with other keys than the forward's,
+    latents that are not bf16 on the GPU, and the single-forward case (both scales 1)."""
+    tea = (tea_cache_posi or {}).get("tea_cache") is not None or (tea_cache_nega or {}).get("tea_cache") is not None
+    return bool(hip is None or tea or use_controlnet or (usp_kwargs or {}).get("use_unified_sequence_parallel") or extra_input
+                or set(prompt_emb_posi) != {"context"} or set(prompt_emb_nega) != {"context"} or not set(image_emb) <= {"clip_feature", "y"}
+                or not getattr(latents, "is_cuda", False) or latents.dtype != torch.bfloat16
+                or (cfg_scale["text"] == 1.0 and cfg_scale["audio"] == 1.0))
+
+
+def _hip_sample_with_multitalk(self, latents, prompt_emb_posi, prompt_emb_nega, image_emb, extra_input, tea_cache_posi, tea_cache_nega, usp_kwargs,
+                               condition, audio_embed_tuple, audio_embed_tuple_null, use_controlnet, cfg_scale, progress_bar_cmd):
+    """SVITalkVideoPipeline._sample_with_multitalk (pipelines/svi_video_talk.py:448-466) with the reference's exact signature, bound onto the pipeline by
+    install(): the clip's steps on DenoiseLoop's talk path — the three guidance forwards of a step as one captured forward_talk3 call, the audio
+    projected once per clip, three-way guidance + Euler update in one fused kernel with the reference's bf16 rounding points.  Bit-identical to the
+    reference's loop over the swapped model_fn_wan_talk_video (tests/test_gpu_talk3.py).  What this loop does not cover goes to the pipeline's original
+    sampler (_talk_sampler_passes_through)."""
+    hip = getattr(self, "_svi_hip_dit", None)
+    if _talk_sampler_passes_through(hip, latents, prompt_emb_posi, prompt_emb_nega, image_emb, extra_input, tea_cache_posi, tea_cache_nega, usp_kwargs,
+                                    use_controlnet, cfg_scale):
+        return self._svi_hip_original_talk_sampler(latents, prompt_emb_posi, prompt_emb_nega, image_emb, extra_input, tea_cache_posi, tea_cache_nega,
+                                                   usp_kwargs, condition, audio_embed_tuple, audio_embed_tuple_null, use_controlnet, cfg_scale,
+                                                   progress_bar_cmd)
+    _assert_resident(self, hip, full=True)           # once per clip: offload switched on / parameters moved since install()
+    loop = self._svi_hip_loop
+    cond = {k: image_emb[k] for k in ("clip_feature", "y") if image_emb.get(k) is not None}
+    if condition is not None:
+        cond["add_condition"] = condition
+    ctx_p, ctx_n = prompt_emb_posi["context"], prompt_emb_nega["context"]
+    if not loop.resident:
+        ctx_p, ctx_n = _stable_bf16(hip, ctx_p), _stable_bf16(hip, ctx_n)
+    with torch.no_grad():
+        return loop._sample_talk3(latents, ctx_p, ctx_n, audio_embed_tuple, audio_embed_tuple_null, float(cfg_scale["text"]), float(cfg_scale["audio"]),
+                                  self.scheduler.timesteps, lambda t: _step_delta_of(self.scheduler, t), progress_bar_cmd, cond)
+
+
 # ------------------------------------------------------------------------------------------------------
 # WanVideoPipeline (pipelines/wan_video.py): its step loop is INLINE in __call__ (:266-278), so there is no sampler method to rebind.  Everything around
 # the loop — parameter check, scheduler, seeded noise, prompt / image encoding, TeaCache construction, decode, tensor2video (:197-264, :280-290) — must keep
@@ -709,11 +816,19 @@ def _route_dit(pipe, hip, sampler: bool = True) -> None:
         if not hasattr(mod, "_svi_hip_original_talk_fn"):
             mod._svi_hip_original_talk_fn = mod.model_fn_wan_talk_video
         mod.model_fn_wan_talk_video = _hip_talk_fn
+    own_sampler = False
     if sampler and hasattr(type(pipe), "_sample_with_regular_video"):
         pipe._svi_hip_original_sampler = types.MethodType(type(pipe)._sample_with_regular_video, pipe)
         pipe._svi_hip_loop = DenoiseLoop(hip, scheduler=getattr(pipe, "scheduler", None), resident=True)
         pipe._sample_with_regular_video = types.MethodType(_hip_sample_with_regular_video, pipe)
-    elif sampler:
+        own_sampler = True
+    if sampler and hasattr(type(pipe), "_sample_with_multitalk"):      # SVITalkVideoPipeline (svi_video_talk.py:448): the three-forward sampler
+        pipe._svi_hip_original_talk_sampler = types.MethodType(type(pipe)._sample_with_multitalk, pipe)
+        if not own_sampler:
+            pipe._svi_hip_loop = DenoiseLoop(hip, scheduler=getattr(pipe, "scheduler", None), resident=True)
+        pipe._sample_with_multitalk = types.MethodType(_hip_sample_with_multitalk, pipe)
+        own_sampler = True
+    if sampler and not own_sampler:
         _route_wan_call(pipe, hip)                     # WanVideoPipeline: the loop is inline in __call__ (wan_video.py:266-278)
 
 
@@ -798,7 +913,8 @@ def install(pipe, vae: bool = True, encoders: bool = True, sampler: bool = True,
     * with `sampler`: `pipe._sample_with_regular_video` (svi_video.py:392-421) is rebound to the DenoiseLoop-backed sampler of the same
       signature — one C call for the two forwards of a step, fused CFG + Euler kernel: the loop bench.py times; a WanVideoPipeline, whose loop is
       inline in `__call__` (wan_video.py:266-278), gets the same loop through `_hip_wan_pipeline_call` (the reference's own `__call__` keeps running
-      around it: every line outside the loop is the reference's);
+      around it: every line outside the loop is the reference's); an SVITalkVideoPipeline's `_sample_with_multitalk` (svi_video_talk.py:448-466) is
+      rebound to `_hip_sample_with_multitalk` — the three guidance forwards of a step as one captured call, the audio projected once per clip;
     * `pipe.vae.encode/decode` are rebound to the HIP VAE (same signatures), when `vae` is true; `vae_split` = (parts_h, parts_w) (+ `vae_group`, whose
       ranks each decode one part; a group alone takes default_vae_split's grid) makes every decode the exact spatial split of WanVideoVAE.decode —
       off by default; call the pipeline with tiled=False then, the blended tiling and the split exclude each other; `vae_encode_split` (a grid, or

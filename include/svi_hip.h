@@ -164,6 +164,35 @@ svi_status svi_dit_audio_slot(svi_dit* h, int32_t slot /* 0 or 1 */, const void*
 svi_status svi_dit_forward_talk3(svi_dit* h, const void* x, const float* timestep, const void* context_cond, const void* context_uncond,
                                  const void* clip_feature, const void* y, const void* add_condition, void* out_cond, void* out_uncond,
                                  void* out_drop_text, int32_t T, int32_t H, int32_t W, int32_t Lc, svi_stream stream);
+/* The talk step with TeaCache (additive in v13): svi_dit_forward_talk3 plus svi_dit_forward_tea's modes, one per branch, and one residual bf16 [1, L, dim]
+ * per branch.  Per branch k = cond, uncond, drop_text:
+ *   0: run the blocks; residual_k is ignored (may be NULL).
+ *   1 (store): run the blocks and write residual_k = bf16(x_after_blocks_k - x_before_blocks_k).
+ *   2 (skip): run no block and read no audio slot; the head reads bf16(x_before_blocks_k + residual_k).
+ * x_before_blocks_k is the branch's own embedded input: the patch embedding for uncond, bf16(patch embedding + add_condition) for cond and drop_text — two
+ * branches that skip from the same residual still differ wherever add_condition is given.  Rounding points as svi_dit_forward_tea; all modes 0 is
+ * svi_dit_forward_talk3 itself.
+ * The reference consults ONE negative TeaCache object twice per step (svi_video_talk.py:448-466: uncond, then drop-text), so residual_uncond and
+ * residual_drop_text may be THE SAME buffer.  The branches take effect in the order cond, uncond, drop_text on the caller's stream, and so do the reads and
+ * writes of a shared buffer: a skipping drop_text reads what uncond stored in this call; a skipping uncond reads the old values before drop_text's store
+ * overwrites them; of two stores drop_text's is what remains.
+ * Shared among the branches that run their blocks, as in svi_dit_forward_talk3: the timestep stage and the patch embedding (once per call, also for the
+ * skipping branches), block 0's self-attention once per distinct embedded input, the audio K / V^T of the slots.  The skipping branches are served by one
+ * row kernel — a row of the patch embedding read once, the add_condition row where a skipping branch has one, each skipping branch's residual row; it writes
+ * the head's LayerNorm + modulate row per branch with svi_dit_forward_tea's bits — then the head projection and unpatchify per branch.  uncond and drop_text
+ * skipping from the same buffer without add_condition are equal by construction: computed once, written twice.
+ * The patch embedding is kept in a buffer of its own, L x dim x 2 B (0.34 GB at 32760 tokens and the 14B width), allocated by the first call with a mode
+ * other than 0 (svi_dit_generation moves; refused while the stream is being captured), so every mode pattern after it runs on the same addresses and can be
+ * captured into a hipGraph.
+ * Refused (SVI_ERR_INVALID, the message names the argument): a mode outside 0..2; a NULL or misaligned (16 B) residual where the mode is 1 or 2;
+ * residual_cond overlapping either of the others; residual_uncond and residual_drop_text overlapping without being identical; a residual overlapping an
+ * output, x or an audio slot; and everything svi_dit_forward_talk3 refuses — unstaged or mis-sized slots also when every branch skips, so that a mode
+ * pattern cannot change which calls are legal.  Each output and residual is bit-identical to svi_dit_forward_tea calls in the order cond, uncond, drop_text
+ * with that branch's audio armed. */
+svi_status svi_dit_forward_talk3_tea(svi_dit* h, const void* x, const float* timestep, const void* context_cond, const void* context_uncond,
+                                     const void* clip_feature, const void* y, const void* add_condition, void* out_cond, void* out_uncond,
+                                     void* out_drop_text, int32_t T, int32_t H, int32_t W, int32_t Lc, int32_t tea_cond, int32_t tea_uncond,
+                                     int32_t tea_drop_text, void* residual_cond, void* residual_uncond, void* residual_drop_text, svi_stream stream);
 
 /* TeaCache support (pipelines/svi_video.py:23-72 class TeaCache, :117-131 its use inside model_fn_wan_video).
  * svi_dit_time_mod: t_mod bf16 [B, 6, dim], the tensor TeaCache.check() compares between steps (host logic decides).

@@ -324,6 +324,12 @@ svi_status svi_launch_sub_bf16(bf16* out, const bf16* a, const bf16* b, int64_t 
 // out_k = modulate(LayerNorm(bf16(x + res_k))) for one or two residuals over the same rows of x (the TeaCache skip step of a CFG pair); res_b / out_b may be null
 svi_status svi_launch_add_ln_mod_pair(const bf16* x, const bf16* res_a, const bf16* res_b, bf16* out_a, bf16* out_b, int rows, int dim, float eps,
                                       const float* shift, const float* scale1p, hipStream_t st);
+// out = bf16(a - bf16(b + c)) (n a multiple of 8, operands 16-byte aligned): a TeaCache residual against x_before_blocks = bf16(patch embedding + add_condition)
+svi_status svi_launch_sub_sum_bf16(bf16* out, const bf16* a, const bf16* b, const bf16* c, int64_t n, hipStream_t st);
+// the talk step's counterpart: out[k] = modulate(LayerNorm(bf16(x_k + res[k]))) for every branch k (cond, uncond, drop-text) whose res[k] is given, with
+// x_k = bf16(x + add_condition) where with_addc[k] (and add_condition is given), else x
+svi_status svi_launch_add_ln_mod_talk3(const bf16* x, const bf16* add_condition, const bf16* const res[3], bf16* const out[3], const bool with_addc[3],
+                                       int rows, int dim, float eps, const float* shift, const float* scale1p, hipStream_t st);
 svi_status svi_launch_fp8_e4m3_to_bf16(const unsigned char* in, bf16* out, int64_t n, hipStream_t st);
 // fp32 C[M,N] = A[M,K] W[N,K]^T + bias[N] (+ res[M,N]) on the exact-fp32 MFMA kernel of the VAE (csrc/svi_vae.hip)
 svi_status svi_launch_gemm_f32(const float* A, int lda, const float* W, int ldw, const float* bias, float* C, int ldc, int M, int N, int K,

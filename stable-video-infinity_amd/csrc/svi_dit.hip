@@ -89,6 +89,7 @@ struct CtxKV { bf16 *CK, *CVT, *CKi, *CVTi; bool compute; const int* tail; int k
 // forward armed through svi_dit_set_audio re-projects them.  The slot owns its buffers: the caller's windows are read while it is staged, never later.
 struct AudSlot {
     char* base = nullptr;
+    size_t bytes = 0;               // of the allocation at `base`
     int frames = 0;                 // latent frames the allocation is laid out for
     bool staged = false;            // false after a weight was bound: the projections were made with the old values
     int ld = 0;
@@ -135,6 +136,10 @@ struct svi_dit {
     bf16 *AH0 = nullptr, *AH1 = nullptr, *AP3 = nullptr, *AUD = nullptr, *AK = nullptr, *AVT = nullptr;
     int ldavt = 0;
     AudSlot aud_slot[2];              // svi_dit_audio_slot: 0 = the clip's audio, 1 = the null audio (svi_dit_forward_talk3)
+    // svi_dit_forward_talk3_tea: the patch embedding x_before_blocks [L, dim] of the step, kept beside X / X2 while the branches run (the stores subtract
+    // it, the skip kernel reads it); allocated by the first call with a mode other than 0, grown when L grows
+    bf16* tea_xb = nullptr;
+    size_t tea_xb_bytes = 0;
     // sequence-parallel shard in flight (svi_dit_sp_begin .. svi_dit_sp_head)
     int sp_rows = 0, sp_row0 = 0, sp_Lc = 0;
     int sp_nb = 1;                    // 2: the shard carries both CFG branches stacked (svi_dit_sp_begin_pair): X = [cond rows | uncond rows]
@@ -286,6 +291,7 @@ extern "C" svi_status svi_dit_destroy(svi_dit* h) {
     if (h->aud_base) (void)hipFree(h->aud_base);
     for (auto& s : h->aud_slot)
         if (s.base) (void)hipFree(s.base);
+    if (h->tea_xb) (void)hipFree(h->tea_xb);
     if (h->rope_dev) (void)hipFree(h->rope_dev);
     for (auto& e : h->ctx_entries)
         if (e.base) (void)hipFree(e.base);
@@ -997,10 +1003,10 @@ static CtxKV kv_of(svi_dit* h, const CtxUse& u, int l) {
 // head (dit:401-404): LN + modulation + Linear(dim -> out_dim * patch volume) on the rows in X -> HO [L, ho_ld]
 static int head_ld(const svi_dit_config& c) { return (c.out_dim * c.patch_t * c.patch_h * c.patch_w + 7) / 8 * 8; }
 // the head's Linear on the normed + modulated rows in Hb
-static svi_status stage_head_project(svi_dit* h, bf16* HO, int L, hipStream_t st, int nb = 1) {
+static svi_status stage_head_project(svi_dit* h, bf16* HO, int L, hipStream_t st, int nb = 1, const bf16* rows = nullptr) {
     const svi_dit_config& c = h->cfg;
     const int ho = c.out_dim * c.patch_t * c.patch_h * c.patch_w;
-    return linear(h->ws.Hb, c.dim, h->head, HO, head_ld(c), L, ho, c.dim, SVI_EPI_BIAS, st, nullptr, nullptr, 0, nb);
+    return linear(rows ? rows : h->ws.Hb, c.dim, h->head, HO, head_ld(c), L, ho, c.dim, SVI_EPI_BIAS, st, nullptr, nullptr, 0, nb);
 }
 static svi_status stage_head_rows(svi_dit* h, bf16* HO, int L, hipStream_t st, int nb = 1) {
     const svi_dit_config& c = h->cfg;
@@ -1204,7 +1210,7 @@ extern "C" svi_status svi_dit_audio_slot(svi_dit* h, int32_t slot, const void* a
         char* base = nullptr;
         hipError_t e = hipMalloc((void**)&base, off);
         if (e != hipSuccess) { svi_set_error("hipMalloc(%zu B audio slot %d) failed: %s", off, slot, hipGetErrorString(e)); return SVI_ERR_OOM; }
-        s.base = base; s.frames = f; s.ld = ld;
+        s.base = base; s.bytes = off; s.frames = f; s.ld = ld;
         SVI_CHECK_HIP(hipMemsetAsync(base, 0, off, st));
         auto P = [&](size_t o) { return reinterpret_cast<bf16*>(base + o); };
         s.H0 = P(oh0); s.H1 = P(oh1); s.P3 = P(op3); s.AUD = P(oaud);
@@ -1271,11 +1277,127 @@ static svi_status forward_talk3(svi_dit* h, const bf16* x, const float* timestep
     return branch(ctx_u, 0, out_d);
 }
 
-extern "C" svi_status svi_dit_forward_talk3(svi_dit* h, const void* x, const float* timestep, const void* context_cond, const void* context_uncond,
-                                            const void* clip_feature, const void* y, const void* add_condition, void* out_cond, void* out_uncond,
-                                            void* out_drop_text, int32_t T, int32_t H, int32_t W, int32_t Lc, svi_stream stream) {
+// x_before_blocks of a TeaCache talk step lives in a buffer of its own beside X / X2 (svi_dit::tea_xb): sized here, outside any capture.
+static svi_status ensure_tea_xb(svi_dit* h, size_t bytes, hipStream_t st) {
+    if (h->tea_xb && h->tea_xb_bytes >= bytes) return SVI_OK;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) {
+        svi_set_error("svi_dit_forward_talk3_tea: the x_before_blocks buffer must grow (%zu B) while the stream is being captured: run this problem size once before the capture", bytes);
+        return SVI_ERR_INVALID;
+    }
+    (void)hipGetLastError();
+    if (h->tea_xb) { SVI_CHECK_HIP(hipFree(h->tea_xb)); h->tea_xb = nullptr; h->tea_xb_bytes = 0; }
+    hipError_t e = hipMalloc((void**)&h->tea_xb, al(bytes));
+    if (e != hipSuccess) { h->tea_xb = nullptr; svi_set_error("hipMalloc(%zu B x_before_blocks) failed: %s", bytes, hipGetErrorString(e)); return SVI_ERR_OOM; }
+    h->tea_xb_bytes = al(bytes);
+    ++h->generation;
+    return SVI_OK;
+}
+
+// The talk step with TeaCache (svi_video_talk.py:448-466; include/svi_hip.h): per branch k = cond, uncond, drop-text, modes[k] 0 = run the blocks, 1 = run
+// them and store ress[k] = bf16(x_after_blocks - x_before_blocks_k), 2 = skip them, the head reads bf16(x_before_blocks_k + ress[k]).  x_before_blocks is the
+// patch embedding E for uncond and bf16(E + add_condition) for cond and drop-text.  E is kept in tea_xb for the whole call: the stores subtract it (with
+// add_condition: svi_launch_sub_sum_bf16, which re-forms the sum at add_bf16's rounding point) and the skip kernel reads it.
+// Order on the stream: uncond's blocks (and store), then ALL skipping branches (one row kernel, then head projection + unpatchify per branch), then cond's
+// and drop-text's blocks (and stores).  uncond and drop-text may share one residual buffer — the reference consults ONE negative cache twice per step —
+// and this order is what that needs: a skipping drop-text reads what uncond stored in this call, a skipping uncond reads the old values before
+// drop-text's store overwrites them, and of two stores drop-text's lands last.  cond's buffer overlaps neither, so its place in the order is free.
+// What the computing branches share is shared as in forward_talk3: block 0's self-attention once per distinct embedded input, X2 its snapshot.
+static svi_status forward_talk3_tea(svi_dit* h, const bf16* x, const float* timestep, const bf16* ctx_c, const bf16* ctx_u, const bf16* clip, const bf16* y,
+                                    const bf16* addc, bf16* const outs[3], int T, int H, int W, int Lc, hipStream_t st, const int modes[3],
+                                    bf16* const ress[3]) {
+    const svi_dit_config& c = h->cfg;
+    const int D = c.dim;
+    const int f = T / c.patch_t, hh = H / c.patch_h, ww = W / c.patch_w;
+    const int L = f * hh * ww;
+    const size_t xbytes = (size_t)L * D * 2;
+    const int64_t n = (int64_t)L * D;
+    SVI_TRY(ensure_workspace(h, L, Lc, st));
+    SVI_TRY(ensure_rope(h, f, hh, ww));
+    SVI_TRY(ensure_tea_xb(h, xbytes, st));
+    Workspace& w = h->ws;
+    bf16* const E = h->tea_xb;
+    SVI_TRY(stage_time(h, timestep, st));
+    SVI_TRY(stage_embed(h, x, y, nullptr, T, H, W, L, st));
+    SVI_CHECK_HIP(hipMemcpyAsync(E, w.X, xbytes, hipMemcpyDeviceToDevice, st));
+    const bf16* const ctxs[3] = {ctx_c, ctx_u, ctx_u};
+    const int slots[3] = {0, 1, 0};
+    const bool with_addc[3] = {true, false, true};
+    // branch k from X = its rows behind block 0's self-attention: the remaining blocks, the store, the head
+    auto branch = [&](int k) -> svi_status {
+        const AudSlot& s = h->aud_slot[slots[k]];
+        CtxUse cu{};
+        SVI_TRY(stage_context(h, ctxs[k], clip, y, Lc, &cu, st));      // (scratch rows of its own: X is untouched)
+        for (int l = 0; l < c.num_layers; ++l) {
+            const AudKV akv{s.K[l], s.VT[l], s.ld};
+            const float* modf = w.modf + (size_t)l * 6 * D;
+            if (l) SVI_TRY(run_block_self(h, l, w.X, modf, L, st));
+            SVI_TRY(run_block_rest(h, l, w.X, cu.CTXp, modf, L, Lc, kv_of(h, cu, l), st, f, 0, hh * ww, &akv));
+        }
+        if (modes[k] == 1) {
+            if (addc && with_addc[k]) SVI_TRY(svi_launch_sub_sum_bf16(ress[k], w.X, E, addc, n, st));
+            else SVI_TRY(svi_launch_sub_bf16(ress[k], w.X, E, n, st));
+        }
+        return stage_head(h, outs[k], T, H, W, L, st);
+    };
+    const bool run_c = modes[0] != 2, run_u = modes[1] != 2, run_d = modes[2] != 2;
+    const int n_cd = (run_c ? 1 : 0) + (run_d ? 1 : 0);
+    const bool snap_shared = !addc && run_u && n_cd > 0;          // without add_condition the three inputs are one: uncond's snapshot serves cond / drop-text
+    if (run_u) {
+        SVI_TRY(run_block_self(h, 0, w.X, w.modf, L, st));
+        if (snap_shared) SVI_CHECK_HIP(hipMemcpyAsync(w.X2, w.X, xbytes, hipMemcpyDeviceToDevice, st));
+        SVI_TRY(branch(1));
+    }
+    if (!run_c || !run_u || !run_d) {
+        // The skipping branches.  Between two branches the blocks' scratch is free: Hb and the two halves of QK [L, 2 dim] take one branch's rows each.
+        // uncond and drop-text skipping from ONE buffer without add_condition are the same rows: computed once, the output copied.
+        const bool twin = !run_u && !run_d && ress[1] == ress[2] && !addc;
+        bf16* const bufs[3] = {w.Hb, w.QK, w.QK + (size_t)L * D};
+        const bf16* sres[3] = {nullptr, nullptr, nullptr};
+        bf16* sout[3] = {nullptr, nullptr, nullptr};
+        int nb = 0;
+        for (int k = 0; k < 3; ++k)
+            if (modes[k] == 2 && !(twin && k == 2)) { sres[k] = ress[k]; sout[k] = bufs[nb++]; }
+        SVI_TRY(svi_launch_add_ln_mod_talk3(E, addc, sres, sout, with_addc, L, D, c.eps, w.headf, w.headf + D, st));
+        for (int k = 0; k < 3; ++k) {
+            if (!sout[k]) continue;
+            SVI_TRY(stage_head_project(h, w.HO, L, st, 1, sout[k]));
+            SVI_TRY(stage_unpatchify(h, w.HO, outs[k], T, H, W, st));
+        }
+        if (twin) SVI_CHECK_HIP(hipMemcpyAsync(outs[2], outs[1], (size_t)c.out_dim * T * H * W * 2, hipMemcpyDeviceToDevice, st));
+    }
+    if (n_cd == 0) return SVI_OK;
+    if (snap_shared) SVI_CHECK_HIP(hipMemcpyAsync(w.X, w.X2, xbytes, hipMemcpyDeviceToDevice, st));
+    else {
+        if (run_u) SVI_CHECK_HIP(hipMemcpyAsync(w.X, E, xbytes, hipMemcpyDeviceToDevice, st));      // uncond's blocks ran on X (else it still holds E)
+        if (addc) SVI_TRY(svi_launch_add_bf16(w.X, addc, n, st));
+        SVI_TRY(run_block_self(h, 0, w.X, w.modf, L, st));
+        if (n_cd == 2) SVI_CHECK_HIP(hipMemcpyAsync(w.X2, w.X, xbytes, hipMemcpyDeviceToDevice, st));
+    }
+    SVI_TRY(branch(run_c ? 0 : 2));
+    if (n_cd == 2) {
+        SVI_CHECK_HIP(hipMemcpyAsync(w.X, w.X2, xbytes, hipMemcpyDeviceToDevice, st));
+        SVI_TRY(branch(2));
+    }
+    return SVI_OK;
+}
+
+// svi_dit_forward_talk3 and svi_dit_forward_talk3_tea: one body (all modes 0 is the plain call)
+static svi_status talk3_entry(svi_dit* h, const void* x, const float* timestep, const void* context_cond, const void* context_uncond,
+                              const void* clip_feature, const void* y, const void* add_condition, void* out_cond, void* out_uncond,
+                              void* out_drop_text, int32_t T, int32_t H, int32_t W, int32_t Lc, const int modes[3], void* const residuals[3],
+                              svi_stream stream) {
     SVI_REQUIRE(h && x && timestep && context_cond && context_uncond, "svi_dit_forward_talk3: null argument");
     SVI_REQUIRE(out_cond && out_uncond && out_drop_text, "svi_dit_forward_talk3: null output");
+    static const char* const mode_arg[3] = {"tea_cond", "tea_uncond", "tea_drop_text"};
+    static const char* const res_arg[3] = {"residual_cond", "residual_uncond", "residual_drop_text"};
+    bool tea = false;
+    for (int k = 0; k < 3; ++k) {
+        SVI_REQUIRE(modes[k] >= 0 && modes[k] <= 2, "svi_dit_forward_talk3_tea: %s = %d (0 = plain, 1 = store, 2 = skip)", mode_arg[k], modes[k]);
+        SVI_REQUIRE(modes[k] == 0 || residuals[k], "svi_dit_forward_talk3_tea: %s = %d needs %s", mode_arg[k], modes[k], res_arg[k]);
+        SVI_REQUIRE(modes[k] == 0 || ((uintptr_t)residuals[k] & 15) == 0, "svi_dit_forward_talk3_tea: %s must be 16-byte aligned", res_arg[k]);
+        tea = tea || modes[k] != 0;
+    }
     SVI_REQUIRE_DEVICE(h);
     const svi_dit_config& c = h->cfg;
     SVI_REQUIRE(c.enable_multitalk, "svi_dit_forward_talk3: the model was created without enable_multitalk");
@@ -1295,11 +1417,58 @@ extern "C" svi_status svi_dit_forward_talk3(svi_dit* h, const void* x, const flo
         SVI_REQUIRE(a.base && a.staged, "svi_dit_forward_talk3: audio slot %d is not staged (svi_dit_audio_slot)", s);
         SVI_REQUIRE(a.frames == f, "svi_dit_forward_talk3: audio slot %d covers %d latent frames, the latents have %d", s, a.frames, f);
     }
+    if (tea) {
+        // the residual buffers [1, L, dim]: cond's apart from the others', uncond's and drop-text's apart or THE SAME buffer (one negative cache consulted
+        // twice per step), and none of them inside anything else the call reads or writes
+        const size_t rbytes = (size_t)f * (H / c.patch_h) * (W / c.patch_w) * c.dim * 2;
+        auto apart = [](uintptr_t a, size_t na, uintptr_t b, size_t nb) { return a + na <= b || b + nb <= a; };
+        const uintptr_t r[3] = {(uintptr_t)residuals[0], (uintptr_t)residuals[1], (uintptr_t)residuals[2]};
+        for (int k = 1; k < 3; ++k)
+            SVI_REQUIRE(!modes[0] || !modes[k] || apart(r[0], rbytes, r[k], rbytes), "svi_dit_forward_talk3_tea: residual_cond overlaps %s", res_arg[k]);
+        SVI_REQUIRE(!modes[1] || !modes[2] || r[1] == r[2] || apart(r[1], rbytes, r[2], rbytes),
+                    "svi_dit_forward_talk3_tea: residual_uncond and residual_drop_text overlap without being the same buffer");
+        const size_t in_bytes = (size_t)16 * T * H * W * 2;
+        static const char* const out_arg[3] = {"out_cond", "out_uncond", "out_drop_text"};
+        for (int k = 0; k < 3; ++k) {
+            if (!modes[k]) continue;
+            for (int j = 0; j < 3; ++j) SVI_REQUIRE(apart(r[k], rbytes, o[j], obytes), "svi_dit_forward_talk3_tea: %s overlaps %s", res_arg[k], out_arg[j]);
+            SVI_REQUIRE(apart(r[k], rbytes, (uintptr_t)x, in_bytes), "svi_dit_forward_talk3_tea: %s overlaps the input x", res_arg[k]);
+            for (int s = 0; s < 2; ++s)
+                SVI_REQUIRE(apart(r[k], rbytes, (uintptr_t)h->aud_slot[s].base, h->aud_slot[s].bytes), "svi_dit_forward_talk3_tea: %s overlaps audio slot %d", res_arg[k], s);
+        }
+    }
     SVI_TRY(svi_dit_check_bound(h));
-    return forward_talk3(h, reinterpret_cast<const bf16*>(x), timestep, reinterpret_cast<const bf16*>(context_cond), reinterpret_cast<const bf16*>(context_uncond),
-                         reinterpret_cast<const bf16*>(clip_feature), reinterpret_cast<const bf16*>(y), reinterpret_cast<const bf16*>(add_condition),
-                         reinterpret_cast<bf16*>(out_cond), reinterpret_cast<bf16*>(out_uncond), reinterpret_cast<bf16*>(out_drop_text), T, H, W, Lc,
-                         reinterpret_cast<hipStream_t>(stream));
+    bf16* const outs[3] = {reinterpret_cast<bf16*>(out_cond), reinterpret_cast<bf16*>(out_uncond), reinterpret_cast<bf16*>(out_drop_text)};
+    if (!tea)
+        return forward_talk3(h, reinterpret_cast<const bf16*>(x), timestep, reinterpret_cast<const bf16*>(context_cond), reinterpret_cast<const bf16*>(context_uncond),
+                             reinterpret_cast<const bf16*>(clip_feature), reinterpret_cast<const bf16*>(y), reinterpret_cast<const bf16*>(add_condition),
+                             outs[0], outs[1], outs[2], T, H, W, Lc, reinterpret_cast<hipStream_t>(stream));
+    bf16* const ress[3] = {modes[0] ? reinterpret_cast<bf16*>(residuals[0]) : nullptr, modes[1] ? reinterpret_cast<bf16*>(residuals[1]) : nullptr,
+                           modes[2] ? reinterpret_cast<bf16*>(residuals[2]) : nullptr};
+    return forward_talk3_tea(h, reinterpret_cast<const bf16*>(x), timestep, reinterpret_cast<const bf16*>(context_cond), reinterpret_cast<const bf16*>(context_uncond),
+                             reinterpret_cast<const bf16*>(clip_feature), reinterpret_cast<const bf16*>(y), reinterpret_cast<const bf16*>(add_condition), outs, T, H,
+                             W, Lc, reinterpret_cast<hipStream_t>(stream), modes, ress);
+}
+
+extern "C" svi_status svi_dit_forward_talk3(svi_dit* h, const void* x, const float* timestep, const void* context_cond, const void* context_uncond,
+                                            const void* clip_feature, const void* y, const void* add_condition, void* out_cond, void* out_uncond,
+                                            void* out_drop_text, int32_t T, int32_t H, int32_t W, int32_t Lc, svi_stream stream) {
+    const int modes[3] = {0, 0, 0};
+    void* const residuals[3] = {nullptr, nullptr, nullptr};
+    return talk3_entry(h, x, timestep, context_cond, context_uncond, clip_feature, y, add_condition, out_cond, out_uncond, out_drop_text, T, H, W, Lc, modes,
+                       residuals, stream);
+}
+
+// The talk step with TeaCache (svi_hip.h): a mode and a residual per branch, in one call.
+extern "C" svi_status svi_dit_forward_talk3_tea(svi_dit* h, const void* x, const float* timestep, const void* context_cond, const void* context_uncond,
+                                                const void* clip_feature, const void* y, const void* add_condition, void* out_cond, void* out_uncond,
+                                                void* out_drop_text, int32_t T, int32_t H, int32_t W, int32_t Lc, int32_t tea_cond, int32_t tea_uncond,
+                                                int32_t tea_drop_text, void* residual_cond, void* residual_uncond, void* residual_drop_text,
+                                                svi_stream stream) {
+    const int modes[3] = {tea_cond, tea_uncond, tea_drop_text};
+    void* const residuals[3] = {residual_cond, residual_uncond, residual_drop_text};
+    return talk3_entry(h, x, timestep, context_cond, context_uncond, clip_feature, y, add_condition, out_cond, out_uncond, out_drop_text, T, H, W, Lc, modes,
+                       residuals, stream);
 }
 
 extern "C" svi_status svi_dit_forward(svi_dit* h, const void* x, const float* timestep, const void* context,

@@ -541,6 +541,33 @@ svi_status svi_launch_sub_bf16(bf16* out, const bf16* a, const bf16* b, int64_t 
     return SVI_OK;
 }
 
+// out = bf16(a - bf16(b + c)): the TeaCache residual of a branch whose x_before_blocks is the patch embedding b plus add_condition c — add_bf16_kernel's
+// rounding point, then sub_bf16_kernel's — without keeping the sum in a buffer (svi_dit_forward_talk3_tea)
+__global__ __launch_bounds__(256) void sub_sum_bf16_kernel(bf16* __restrict__ out, const bf16* __restrict__ a, const bf16* __restrict__ b,
+                                                           const bf16* __restrict__ c, int64_t n8) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += stride) {
+        const bf16x8 av = ld_bf16x8(a + i * 8), bv = ld_bf16x8(b + i * 8), cv = ld_bf16x8(c + i * 8);
+        bf16x8 o;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) o[j] = (bf16)((float)av[j] - (float)(bf16)((float)bv[j] + (float)cv[j]));
+        st_bf16x8(out + i * 8, o);
+    }
+}
+
+// n must be a multiple of 8 and the operands 16-byte aligned (rows of the model width)
+svi_status svi_launch_sub_sum_bf16(bf16* out, const bf16* a, const bf16* b, const bf16* c, int64_t n, hipStream_t st) {
+    SVI_REQUIRE(out && a && b && c, "sub_sum: null operand");
+    SVI_REQUIRE(n % 8 == 0 && (((uintptr_t)out | (uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0, "sub_sum: operands must be 16-byte aligned, n a multiple of 8");
+    if (n <= 0) return SVI_OK;
+    const int64_t n8 = n / 8;
+    int blocks = (int)((n8 + 255) / 256);
+    if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL(sub_sum_bf16_kernel, dim3(blocks), dim3(256), 0, st, out, a, b, c, n8);
+    SVI_LAUNCH_CHECK();
+    return SVI_OK;
+}
+
 svi_status svi_launch_add_bf16(bf16* a, const bf16* b, int64_t n, hipStream_t st) {
     if (n <= 0) return SVI_OK;
     int blocks = (int)((n + 255) / 256);
@@ -639,6 +666,122 @@ svi_status svi_launch_add_ln_mod_pair(const bf16* x, const bf16* res_a, const bf
         hipLaunchKernelGGL(add_ln_mod_pair_kernel<10>, grid, block, 0, st, x, res_a, res_b, out_a, out_b, rows, dim, eps, shift, scale1p);
     else
         hipLaunchKernelGGL(add_ln_mod_pair_kernel<16>, grid, block, 0, st, x, res_a, res_b, out_a, out_b, rows, dim, eps, shift, scale1p);
+    SVI_LAUNCH_CHECK();
+    return SVI_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// TeaCache skip step of the talk variant (svi_video_talk.py:448-466): the three guidance branches see the same patch-embedded row of X; cond and drop-text
+// have add_condition added to it first (add_bf16_kernel's rounding point), uncond has not.  One wave reads the row of X once, the add_condition row once
+// where a skipping branch has one, and per skipping branch its residual row; it forms bf16(x_k + residual_k) and writes that branch's LayerNorm + modulate
+// row.  Statistics and output arithmetic are ln_mod_kernel's, statement for statement, as in add_ln_mod_pair_kernel: each output row has the bits of
+// add_bf16 (+ add_bf16) followed by svi_launch_ln_mod.  A branch with res[k] == nullptr is not served (it runs its blocks, or shares another's row).
+struct SviTalk3Skip {
+    const bf16* res[3];          // cond, uncond, drop-text: the residual rows of a skipping branch, nullptr otherwise
+    bf16* out[3];                // that branch's LayerNorm + modulate rows
+    int addc[3];                 // the branch's embedded input has add_condition added
+};
+template <int MAXC>
+__global__ __launch_bounds__(256) void add_ln_mod_talk3_kernel(const bf16* __restrict__ x, const bf16* __restrict__ addc, SviTalk3Skip p, int rows, int dim,
+                                                               float eps, const float* __restrict__ shift, const float* __restrict__ scale1p) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int nchunk = dim >> 3;
+    const size_t roff = (size_t)row * dim;
+    bf16x8 xv[MAXC], xa[MAXC];          // the row of X, and bf16(x + add_condition)
+#pragma unroll
+    for (int c = 0; c < MAXC; ++c) {
+        const int ci = lane + 64 * c;
+        if (ci < nchunk) {
+            xv[c] = ld_bf16x8(x + roff + ci * 8);
+            xa[c] = xv[c];
+            if (addc) {                                  // uniform over the grid
+                const bf16x8 a = ld_bf16x8(addc + roff + ci * 8);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) xa[c][j] = (bf16)((float)xv[c][j] + (float)a[j]);
+            }
+        }
+    }
+#pragma unroll
+    for (int br = 0; br < 3; ++br) {
+        const bf16* res = p.res[br];
+        bf16* out = p.out[br];
+        if (!res) continue;                              // uniform over the grid
+        const bool with_addc = p.addc[br] != 0;
+        float v[MAXC][8];
+        float s = 0.f;
+#pragma unroll
+        for (int c = 0; c < MAXC; ++c) {
+            const int ci = lane + 64 * c;
+            if (ci < nchunk) {
+                const bf16x8 r = ld_bf16x8(res + roff + ci * 8);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) { v[c][j] = (float)(bf16)((float)(with_addc ? xa[c][j] : xv[c][j]) + (float)r[j]); s += v[c][j]; }
+            } else {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) v[c][j] = 0.f;
+            }
+        }
+        const float mean = wave_sum(s) / (float)dim;
+        float q = 0.f;
+#pragma unroll
+        for (int c = 0; c < MAXC; ++c) {
+            const int ci = lane + 64 * c;
+            if (ci < nchunk) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) { float d = v[c][j] - mean; q += d * d; }
+            }
+        }
+        const float rstd = rsqrtf(wave_sum(q) / (float)dim + eps);
+#pragma unroll
+        for (int c = 0; c < MAXC; ++c) {
+            const int ci = lane + 64 * c;
+            if (ci < nchunk) {
+                const int col = ci * 8;
+                const f32x4 sc0 = *reinterpret_cast<const f32x4*>(scale1p + col), sc1 = *reinterpret_cast<const f32x4*>(scale1p + col + 4);
+                const f32x4 sh0 = *reinterpret_cast<const f32x4*>(shift + col), sh1 = *reinterpret_cast<const f32x4*>(shift + col + 4);
+                bf16x8 o;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    float y = rbf((v[c][j] - mean) * rstd);
+                    y = rbf(rbf(y * (j < 4 ? sc0[j & 3] : sc1[j & 3])) + (j < 4 ? sh0[j & 3] : sh1[j & 3]));
+                    o[j] = (bf16)y;
+                }
+                st_bf16x8(out + roff + col, o);
+            }
+        }
+    }
+}
+
+// x, add_condition (may be null), res[k], out[k]: dense [rows, dim] bf16, 16-byte aligned.  Branch k (0 cond, 1 uncond, 2 drop-text) is served when
+// res[k] is given; with_addc[k] says whether its input is bf16(x + add_condition) (ignored without add_condition).  Only the out[k] are written.
+svi_status svi_launch_add_ln_mod_talk3(const bf16* x, const bf16* add_condition, const bf16* const res[3], bf16* const out[3], const bool with_addc[3],
+                                       int rows, int dim, float eps, const float* shift, const float* scale1p, hipStream_t st) {
+    SVI_REQUIRE(x && shift && scale1p, "add + layernorm (talk): null operand");
+    SVI_REQUIRE(dim % 8 == 0 && dim <= 8192, "add + layernorm (talk): dim %d must be a multiple of 8, at most 8192", dim);
+    SviTalk3Skip p{};
+    uintptr_t bits = (uintptr_t)x | (uintptr_t)add_condition | (uintptr_t)shift | (uintptr_t)scale1p;
+    bool any = false, any_addc = false;
+    for (int k = 0; k < 3; ++k) {
+        if (!res[k]) continue;
+        SVI_REQUIRE(out[k], "add + layernorm (talk): branch %d has a residual and no output rows", k);
+        p.res[k] = res[k]; p.out[k] = out[k]; p.addc[k] = (add_condition && with_addc[k]) ? 1 : 0;
+        bits |= (uintptr_t)res[k] | (uintptr_t)out[k];
+        any = true;
+        any_addc = any_addc || p.addc[k];
+    }
+    SVI_REQUIRE((bits & 15) == 0, "add + layernorm (talk): operands must be 16-byte aligned");
+    if (rows <= 0 || !any) return SVI_OK;
+    const bf16* ac = any_addc ? add_condition : nullptr;          // not read when no served branch has it
+    dim3 grid((rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK), block(256);
+    const int nchunk = dim / 8;
+    if (nchunk <= 64 * 3)
+        hipLaunchKernelGGL(add_ln_mod_talk3_kernel<3>, grid, block, 0, st, x, ac, p, rows, dim, eps, shift, scale1p);
+    else if (nchunk <= 64 * 10)
+        hipLaunchKernelGGL(add_ln_mod_talk3_kernel<10>, grid, block, 0, st, x, ac, p, rows, dim, eps, shift, scale1p);
+    else
+        hipLaunchKernelGGL(add_ln_mod_talk3_kernel<16>, grid, block, 0, st, x, ac, p, rows, dim, eps, shift, scale1p);
     SVI_LAUNCH_CHECK();
     return SVI_OK;
 }

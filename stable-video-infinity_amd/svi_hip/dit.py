@@ -455,13 +455,19 @@ class WanDiT:
 
     def forward_talk3(self, x: torch.Tensor, timestep: torch.Tensor, context_cond: torch.Tensor, context_uncond: torch.Tensor,
                       clip_feature: Optional[torch.Tensor] = None, y: Optional[torch.Tensor] = None, add_condition: Optional[torch.Tensor] = None,
-                      out_cond: Optional[torch.Tensor] = None, out_uncond: Optional[torch.Tensor] = None, out_drop_text: Optional[torch.Tensor] = None):
+                      out_cond: Optional[torch.Tensor] = None, out_uncond: Optional[torch.Tensor] = None, out_drop_text: Optional[torch.Tensor] = None,
+                      tea_modes: Tuple[int, int, int] = (0, 0, 0), residual_cond: Optional[torch.Tensor] = None,
+                      residual_uncond: Optional[torch.Tensor] = None, residual_drop_text: Optional[torch.Tensor] = None):
         """The three guidance forwards of a talk step (SVITalkVideoPipeline._sample_with_multitalk, svi_video_talk.py:455-458) in one call
         (svi_dit_forward_talk3): conditional (context_cond, audio slot 0, add_condition), unconditional (context_uncond, audio slot 1 — the null
         audio —, no add_condition), drop-text (context_uncond, audio slot 0, add_condition).  The audio comes from the slots (stage_audio) — nothing
         may be armed through set_audio.  What the branches share is computed once (timestep embedding, patch embedding, block 0's self-attention
         per distinct embedded input; every block's audio K / V^T were projected when the slots were staged); each output is bit-identical to
-        model_fn_wan_talk_video with that branch's inputs.  One sample per call, as the talk variant's forward."""
+        model_fn_wan_talk_video with that branch's inputs.  One sample per call, as the talk variant's forward.
+        tea_modes = (cond, uncond, drop-text) / residual_*: TeaCache per branch (svi_dit_forward_talk3_tea), as forward()'s tea_mode / residual: 1 = also
+        write the branch's residual [1, L, dim], 2 = skip the blocks and add the residual instead.  residual_uncond and residual_drop_text may be one
+        tensor (the reference's one negative cache, consulted twice per step): the branches take effect in the order cond, uncond, drop-text.  At the
+        default, (0, 0, 0), this is the plain call."""
         if not x.is_cuda:
             raise RuntimeError("svi_hip runs on the GPU only")
         if context_cond.shape != context_uncond.shape:
@@ -489,6 +495,20 @@ class WanDiT:
             elif not o.is_cuda or o.dtype != torch.bfloat16 or not o.is_contiguous() or tuple(o.shape) != shape:
                 raise ValueError(f"{name} must be a contiguous CUDA bf16 tensor of shape {shape} (got {tuple(o.shape)}, {o.dtype}, {o.device})")
             outs.append(o)
+        modes = tuple(int(m) for m in tea_modes)
+        if len(modes) != 3:
+            raise ValueError(f"tea_modes takes one mode per branch (cond, uncond, drop-text), got {tea_modes!r}")
+        if any(modes):
+            residuals = (residual_cond, residual_uncond, residual_drop_text)
+            for name, m, r in zip(("residual_cond", "residual_uncond", "residual_drop_text"), modes, residuals):
+                if m and (r is None or not r.is_cuda or r.dtype != torch.bfloat16 or not r.is_contiguous() or r.numel() != self.tokens(T, H, W) * self.dim):
+                    raise ValueError(f"tea_modes {modes} needs {name}: a contiguous CUDA bf16 tensor of shape [1, L, dim]")
+            L.check(L.lib().svi_dit_forward_talk3_tea(self._h, L.ptr(x), L.ptr(timestep), L.ptr(context_cond), L.ptr(context_uncond), L.ptr(clip_feature),
+                                                      L.ptr(y), L.ptr(add_condition), L.ptr(outs[0]), L.ptr(outs[1]), L.ptr(outs[2]), T, H, W,
+                                                      context_cond.shape[1], modes[0], modes[1], modes[2],
+                                                      *(L.ptr(r) if m else None for m, r in zip(modes, residuals)), L.current_stream()),
+                    "svi_dit_forward_talk3_tea")
+            return tuple(outs)
         L.check(L.lib().svi_dit_forward_talk3(self._h, L.ptr(x), L.ptr(timestep), L.ptr(context_cond), L.ptr(context_uncond), L.ptr(clip_feature),
                                               L.ptr(y), L.ptr(add_condition), L.ptr(outs[0]), L.ptr(outs[1]), L.ptr(outs[2]), T, H, W,
                                               context_cond.shape[1], L.current_stream()), "svi_dit_forward_talk3")

@@ -44,6 +44,13 @@ def _release_stream_buffers(stream) -> bool:
 # (profiles/teacache_graph_ab.txt).
 TEA_GRAPH_BY_DEFAULT = True
 
+# The talk step with TeaCache has one captured graph per mode triple (cond, uncond, drop-text).  A positive and a negative cache can produce all eight
+# triples of {store, skip}; a clip lives on few of them: the step on which everything computes — (1, 1, 1), or (1, 1, 2) when the negative cache's second
+# check of the step, on an unchanged t_mod, already skips —, the all-skip step (2, 2, 2), and a transitional triple or two where the negative cache, which is
+# consulted twice per step and so fills its budget sooner, computes a step before the positive one.  Four graphs hold these; a fifth triple evicts the
+# least recently used one, which is captured again if it returns (tests/test_gpu_talk3_tea.py cycles through more).
+TALK_TEA_GRAPHS = 4
+
 
 class DenoiseLoop:
     """50 x { cond forward, uncond forward, CFG combine, Euler step } with latents resident in HBM."""
@@ -93,6 +100,7 @@ class DenoiseLoop:
         self._tea_graphs: Dict[tuple, dict] = {}      # TeaCache: (mode of the conditional branch, of the unconditional) -> the same dict; at most two alive
         self._tea_res: Dict[str, torch.Tensor] = {}   # the loop's residual tensor per branch (a resident loop keeps them in _slots: their addresses survive a clip boundary)
         self.tea_counts = {"computed": 0, "skipped": 0}      # TeaCache steps since the last sample() began, by the conditional branch's decision
+        self.talk_tea_counts: Dict[tuple, int] = {}          # the talk loop's TeaCache steps since the last clip began, by mode triple (cond, uncond, drop-text)
         self._capture_stream = None   # ONE side stream per loop, reused by every re-capture: the library keeps per-stream scratch (flag words,
                                       # split-K partials) for good, so a fresh pool stream per capture would multiply it
 
@@ -260,10 +268,29 @@ class DenoiseLoop:
         self._replay_or_capture(slot, key, tensors, latents.device, timestep,
                                 lambda ts: self._forwards(latents, ts, ctx_pos, ctx_neg, cfg_scale, split, cond, ucond, tea))
 
-    def _replay_or_capture(self, slot, key, tensors, device, timestep, run) -> None:
+    def _held_graph(self, slot, lru: bool = False):
+        """The graph held under `slot` (None: the plain step's), or None; with `lru` the look-up counts as a use."""
+        if slot is None:
+            return self._graph
+        held = self._tea_graphs.get(slot)
+        if lru and held is not None:
+            self._tea_graphs[slot] = self._tea_graphs.pop(slot)      # most recently used: last
+        return held
+
+    def _keep_tea_graph(self, slot, held, bound: int) -> None:
+        """Hold a TeaCache graph under `slot`, at most `bound` of them: the first in the dict's order goes (the oldest capture; the least recently used
+        one where the look-ups count as uses)."""
+        self._graph = None
+        self._tea_graphs.pop(slot, None)
+        while len(self._tea_graphs) >= bound:    # caches that disagree can ask for a third mode: the oldest goes
+            self._tea_graphs.pop(next(iter(self._tea_graphs)))
+        self._tea_graphs[slot] = held
+
+    def _replay_or_capture(self, slot, key, tensors, device, timestep, run, bound: int = 2, lru: bool = False) -> None:
         """Replay the graph held under `slot` while `key` and the DiT's generation still hold; else run `run(timestep tensor)` eagerly on the loop's
-        capture stream — it IS this step — and record it right behind itself.  See _forwards_graphed for the rules."""
-        held = self._graph if slot is None else self._tea_graphs.get(slot)
+        capture stream — it IS this step — and record it right behind itself.  See _forwards_graphed for the rules.  At most `bound` TeaCache graphs
+        stay alive; with `lru` a replay counts as a use, so the one evicted is the least recently used (else the oldest capture)."""
+        held = self._held_graph(slot, lru)
         stale = held is None or held["key"] != key or held["generation"] != self.dit.generation()
         if stale:
             if slot is None:
@@ -296,10 +323,7 @@ class DenoiseLoop:
                 self._graph = held
                 self._tea_graphs.clear()                 # a loop is used with TeaCache or without: the other kind's graphs go
             else:
-                self._graph = None
-                while len(self._tea_graphs) >= 2:        # caches that disagree can ask for a third mode: the oldest goes
-                    self._tea_graphs.pop(next(iter(self._tea_graphs)))
-                self._tea_graphs[slot] = held
+                self._keep_tea_graph(slot, held, bound)
             self.captures += 1
             return
         held["ts"].copy_(timestep)
@@ -392,20 +416,33 @@ class DenoiseLoop:
     @torch.no_grad()
     def sample_multitalk(self, latents: torch.Tensor, ctx_pos: torch.Tensor, ctx_neg: torch.Tensor, audio_embed_tuple, audio_embed_tuple_null,
                          num_inference_steps: int = 50, text_scale: float = 5.0, audio_scale: float = 4.0, sigma_shift: float = 5.0,
-                         denoising_strength: float = 1.0, progress_bar_cmd: Callable = lambda x: x, add_condition=None, **cond) -> torch.Tensor:
+                         denoising_strength: float = 1.0, progress_bar_cmd: Callable = lambda x: x, add_condition=None,
+                         tea_cache_l1_thresh: Optional[float] = None, tea_cache_model_id: str = "", tea_cache_posi=None, tea_cache_nega=None,
+                         **cond) -> torch.Tensor:
         """SVITalkVideoPipeline._sample_with_multitalk (svi_video_talk.py:448-463): per step three forwards — conditional (prompt, audio,
         add_condition), unconditional (negative prompt, null audio, no add_condition), drop-text (negative prompt, audio, add_condition) —
         combined as uncond + text*(cond - drop_text) + audio*(drop_text - uncond); one forward when both scales are 1.
         A loop built with sequence_parallel=True (+ sp_group) runs each of the three forwards on this rank's sequence shard
         (model_fn_wan_talk_video with use_unified_sequence_parallel): every rank ends with the full noise predictions and the same latents.
-        A single-rank loop with `graph` on (the default) and three forwards to run takes the one-call step instead (_sample_talk3): same bits."""
+        A single-rank loop with `graph` on (the default) and three forwards to run takes the one-call step instead (_sample_talk3): same bits.
+        TeaCache as SVITalkVideoPipeline.__call__ sets it up (svi_video_talk.py:541-542, 448-466): tea_cache_l1_thresh (+ tea_cache_model_id) builds one
+        object for the conditional forward and ONE for the unconditional and the drop-text forward — consulted twice per step, in that order —, or the
+        objects are given (tea_cache_posi / tea_cache_nega: svi_hip.TeaCache or the reference's class; None leaves that side without).  The one-call
+        step serves them too (one forward_talk3(tea_modes) call per step, a graph per mode triple); one object given for BOTH sides keeps the eager
+        forwards (the conditional residual would be the negative one's buffer, which the one call refuses)."""
         from .dit import model_fn_wan_talk_video
-        if self.graph and self.cfg_pair is None and not self.sequence_parallel and (text_scale != 1.0 or audio_scale != 1.0):
+        if tea_cache_l1_thresh is not None and tea_cache_posi is None and tea_cache_nega is None:
+            from .teacache import TeaCache
+            tea_cache_posi = TeaCache(num_inference_steps, tea_cache_l1_thresh, tea_cache_model_id)
+            tea_cache_nega = TeaCache(num_inference_steps, tea_cache_l1_thresh, tea_cache_model_id)
+        tea = None if tea_cache_posi is None and tea_cache_nega is None else (tea_cache_posi, tea_cache_nega)
+        one_call = self.graph and self.cfg_pair is None and not self.sequence_parallel and (text_scale != 1.0 or audio_scale != 1.0)
+        if one_call and (tea is None or tea_cache_posi is not tea_cache_nega):
             self.scheduler.set_timesteps(num_inference_steps, denoising_strength=denoising_strength, shift=sigma_shift)
             if add_condition is not None:
                 cond = dict(cond, add_condition=add_condition)
             return self._sample_talk3(latents, ctx_pos, ctx_neg, audio_embed_tuple, audio_embed_tuple_null, text_scale, audio_scale,
-                                      self.scheduler.timesteps, self.scheduler.step_delta, progress_bar_cmd, cond)
+                                      self.scheduler.timesteps, self.scheduler.step_delta, progress_bar_cmd, cond, tea=tea)
         fn = model_fn_wan_talk_video
         if self.sequence_parallel:
             self.dit.sp_group = self.sp_group
@@ -423,10 +460,10 @@ class DenoiseLoop:
         try:
             for i, t in enumerate(progress_bar_cmd(self.scheduler.timesteps)):
                 tt, ds = ts_dev[i:i + 1], self.scheduler.step_delta(t)
-                c = fn(self.dit, latents, tt, ctx_pos, add_condition=add_condition, audio_embed_tuple=aud, **cond)
+                c = fn(self.dit, latents, tt, ctx_pos, add_condition=add_condition, audio_embed_tuple=aud, tea_cache=tea_cache_posi, **cond)
                 if text_scale != 1.0 or audio_scale != 1.0:
-                    u = fn(self.dit, latents, tt, ctx_neg, audio_embed_tuple=aud0, **cond)
-                    d = fn(self.dit, latents, tt, ctx_neg, add_condition=add_condition, audio_embed_tuple=aud, **cond)
+                    u = fn(self.dit, latents, tt, ctx_neg, audio_embed_tuple=aud0, tea_cache=tea_cache_nega, **cond)
+                    d = fn(self.dit, latents, tt, ctx_neg, add_condition=add_condition, audio_embed_tuple=aud, tea_cache=tea_cache_nega, **cond)
                     ops.cfg3_step_(latents, c, u, d, text_scale, audio_scale, ds)
                 else:
                     ops.cfg_step_(latents, c, None, 1.0, ds)
@@ -434,23 +471,67 @@ class DenoiseLoop:
             self.dit.context_cache(False)
         return latents
 
-    def _talk3_graphed(self, latents, timestep, ctx_pos, ctx_neg, cond) -> None:
+    def _talk3_graphed(self, latents, timestep, ctx_pos, ctx_neg, cond, tea=None) -> None:
         """The three forwards of one talk step into self._cond / _uncond / _drop: the captured forward_talk3 call replayed, captured on first use
         (_replay_or_capture, under _forwards_graphed's rules; the key is _graph_key's plus the third output — the audio slots' buffers are the DiT's:
-        its generation() covers them, and a slot rewritten in place for the next clip leaves it alone)."""
+        its generation() covers them, and a slot rewritten in place for the next clip leaves it alone).
+        `tea` = (mode triple, residual per branch) of _talk_tea_decide: the triple has a graph of its own (slot ("talk3", cond, uncond, drop-text)), the
+        triple and the residual tensors' identities are part of its key."""
         self.dit._refresh_if_weights_changed()          # (a re-bind drops the audio slots: forward_talk3 then refuses by name — stage them again)
         _, key, tensors = self._graph_key(latents, ctx_pos, ctx_neg, 0.0, False, cond)
         d = self._drop
         key += ("talk3", (d.data_ptr(), tuple(d.shape), d.dtype, _version(d)))
-        self._replay_or_capture(None, key, tensors + [d], latents.device, timestep,
+        if tea is None:
+            self._replay_or_capture(None, key, tensors + [d], latents.device, timestep,
+                                    lambda ts: self.dit.forward_talk3(latents, ts, ctx_pos, ctx_neg, out_cond=self._cond, out_uncond=self._uncond,
+                                                                      out_drop_text=self._drop, **cond))
+            return
+        modes, residuals = tea
+        key += (modes, tuple(None if r is None else (r.data_ptr(), tuple(r.shape), r.dtype) for r in residuals))
+        self._replay_or_capture(("talk3",) + modes, key, tensors + [d] + [r for r in residuals if r is not None], latents.device, timestep,
                                 lambda ts: self.dit.forward_talk3(latents, ts, ctx_pos, ctx_neg, out_cond=self._cond, out_uncond=self._uncond,
-                                                                  out_drop_text=self._drop, **cond))
+                                                                  out_drop_text=self._drop, tea_modes=modes, residual_cond=residuals[0],
+                                                                  residual_uncond=residuals[1], residual_drop_text=residuals[2], **cond),
+                                bound=TALK_TEA_GRAPHS, lru=True)
+
+    def _talk_tea_decide(self, latents, timestep, tea_posi, tea_nega):
+        """The TeaCache decisions of one talk step, on the host, before anything of the step is enqueued, in the reference's order (svi_video_talk.py:
+        448-466): the positive object for cond, then the negative object for uncond, then the SAME negative object for drop-text — each through its own
+        check(dit, token, t_mod), as _tea_decide.  Returns (modes, residuals) per branch: 2 + the object's previous_residual for a skip, 1 + the loop's
+        residual tensor of that object for a computed step, 0 + None without an object.  A computed decision sets the object's previous_residual to
+        the loop's tensor at once — model_fn_wan_talk_video would have stored before the next forward's check —, so a drop-text branch that skips
+        right behind a computing uncond branch gets the buffer uncond writes in this very call."""
+        t_mod = self.dit.time_mod(timestep)
+        B, _, T, H, W = latents.shape
+        shape = (B, self.dit.tokens(T, H, W), self.dit.dim)
+        modes, residuals = [], []
+        for name, cache in (("talk_posi", tea_posi), ("talk_nega", tea_nega), ("talk_nega", tea_nega)):
+            if cache is None:
+                mode, res = 0, None
+            elif cache.check(self.dit, t_mod[:, :1, :1], t_mod):
+                mode, res = 2, cache.previous_residual
+                if res is None:
+                    raise RuntimeError("TeaCache asked to skip before any residual was stored")
+            else:
+                mode, res = 1, self._tea_residual(name, shape, latents.device)
+                cache.previous_residual = res          # what TeaCache.store() would have computed (svi_video.py:64-66), as model_fn_wan_video leaves it
+                cache.previous_hidden_states = None
+            modes.append(mode)
+            residuals.append(res)
+        modes = tuple(modes)
+        self.talk_tea_counts[modes] = self.talk_tea_counts.get(modes, 0) + 1
+        if tea_posi is not None:
+            self.tea_counts["skipped" if modes[0] == 2 else "computed"] += 1
+        return modes, tuple(residuals)
 
     def _sample_talk3(self, latents, ctx_pos, ctx_neg, audio_embed_tuple, audio_embed_tuple_null, text_scale, audio_scale, timesteps, step_delta,
-                      progress_bar_cmd, cond) -> torch.Tensor:
+                      progress_bar_cmd, cond, tea=None) -> torch.Tensor:
         """The talk clip on the graphed path: both audio tuples are projected into the DiT's audio slots once, then every step is one forward_talk3
         (replayed from the first step's capture) plus the fused three-way guidance + Euler kernel.  `cond`: clip_feature, y, add_condition.  A resident
-        loop copies the clip's inputs into its own tensors (adopt) and re-stages the slots where they stand: the next clip of the same shapes replays."""
+        loop copies the clip's inputs into its own tensors (adopt) and re-stages the slots where they stand: the next clip of the same shapes replays.
+        `tea`: (positive, negative) TeaCache objects, either may be None — the step's three decisions are taken first (_talk_tea_decide), then ONE
+        forward_talk3(tea_modes) call runs, replayed from the graph of its mode triple (at most TALK_TEA_GRAPHS alive, the least recently used evicted);
+        the two residual tensors are the loop's, slots on a resident loop.  talk_tea_counts counts the clip's steps per triple."""
         resident = self.resident
         dev = latents.device
         if resident:
@@ -473,8 +554,11 @@ class DenoiseLoop:
                 self._uncond = torch.empty_like(latents)
             if self._drop is None or self._drop.shape != latents.shape:
                 self._drop = torch.empty_like(latents)
+            self.talk_tea_counts = {}
+            self.tea_counts = {"computed": 0, "skipped": 0}
             for i, t in enumerate(progress_bar_cmd(timesteps)):
-                self._talk3_graphed(latents, ts_dev[i:i + 1], ctx_pos, ctx_neg, cond)
+                decided = None if tea is None else self._talk_tea_decide(latents, ts_dev[i:i + 1], tea[0], tea[1])
+                self._talk3_graphed(latents, ts_dev[i:i + 1], ctx_pos, ctx_neg, cond, decided)
                 ops.cfg3_step_(latents, self._cond, self._uncond, self._drop, text_scale, audio_scale, step_delta(timesteps[i]))
         finally:
             if not resident:
@@ -647,16 +731,39 @@ def _talk_sampler_passes_through(hip, latents, prompt_emb_posi, prompt_emb_nega,
                 or (cfg_scale["text"] == 1.0 and cfg_scale["audio"] == 1.0))
 
 
+def _talk_sampler_tea(tea_cache_posi, tea_cache_nega):
+    """The (positive, negative) TeaCache objects SVITalkVideoPipeline.__call__ built for a clip (svi_video_talk.py:541-542), or None when neither dict
+    carries one."""
+    posi, nega = (tea_cache_posi or {}).get("tea_cache"), (tea_cache_nega or {}).get("tea_cache")
+    return None if posi is None and nega is None else (posi, nega)
+
+
+def _talk_sampler_serves_tea(hip, latents, prompt_emb_posi, prompt_emb_nega, image_emb, extra_input, tea_cache_posi, tea_cache_nega, usp_kwargs,
+                             use_controlnet, cfg_scale) -> bool:
+    """install()'s talk sampler serves a clip with TeaCache objects itself (DenoiseLoop._sample_talk3(tea=...)) when the objects are the ONLY reason
+    _talk_sampler_passes_through hands the clip back: that rule, asked with the two TeaCache dicts emptied, must let the clip through.  One object
+    in both dicts stays with the pipeline's loop (sample_multitalk says why)."""
+    tea = _talk_sampler_tea(tea_cache_posi, tea_cache_nega)
+    return bool(tea is not None and tea[0] is not tea[1]
+                and not _talk_sampler_passes_through(hip, latents, prompt_emb_posi, prompt_emb_nega, image_emb, extra_input, {}, {}, usp_kwargs,
+                                                     use_controlnet, cfg_scale))
+
+
 def _hip_sample_with_multitalk(self, latents, prompt_emb_posi, prompt_emb_nega, image_emb, extra_input, tea_cache_posi, tea_cache_nega, usp_kwargs,
                                condition, audio_embed_tuple, audio_embed_tuple_null, use_controlnet, cfg_scale, progress_bar_cmd):
     """SVITalkVideoPipeline._sample_with_multitalk (pipelines/svi_video_talk.py:448-466) with the reference's exact signature, bound onto the pipeline by
     install(): the clip's steps on DenoiseLoop's talk path — the three guidance forwards of a step as one captured forward_talk3 call, the audio
     projected once per clip, three-way guidance + Euler update in one fused kernel with the reference's bf16 rounding points.  Bit-identical to the
     reference's loop over the swapped model_fn_wan_talk_video (tests/test_gpu_talk3.py).  What this loop does not cover goes to the pipeline's original
-    sampler (_talk_sampler_passes_through)."""
+    sampler (_talk_sampler_passes_through) — except a clip whose only reason to go there is a TeaCache object (_talk_sampler_serves_tea): the objects the
+    pipeline built drive the loop's one-call step through their own check() and end the clip as the pipeline's loop would have left them
+    (previous_residual: the same values, in the loop's tensor)."""
     hip = getattr(self, "_svi_hip_dit", None)
-    if _talk_sampler_passes_through(hip, latents, prompt_emb_posi, prompt_emb_nega, image_emb, extra_input, tea_cache_posi, tea_cache_nega, usp_kwargs,
-                                    use_controlnet, cfg_scale):
+    serves_tea = _talk_sampler_serves_tea(hip, latents, prompt_emb_posi, prompt_emb_nega, image_emb, extra_input, tea_cache_posi, tea_cache_nega,
+                                          usp_kwargs, use_controlnet, cfg_scale) and getattr(self, "_svi_hip_loop", None) is not None \
+        and self._svi_hip_loop.graph
+    if not serves_tea and _talk_sampler_passes_through(hip, latents, prompt_emb_posi, prompt_emb_nega, image_emb, extra_input, tea_cache_posi,
+                                                       tea_cache_nega, usp_kwargs, use_controlnet, cfg_scale):
         return self._svi_hip_original_talk_sampler(latents, prompt_emb_posi, prompt_emb_nega, image_emb, extra_input, tea_cache_posi, tea_cache_nega,
                                                    usp_kwargs, condition, audio_embed_tuple, audio_embed_tuple_null, use_controlnet, cfg_scale,
                                                    progress_bar_cmd)
@@ -670,7 +777,8 @@ def _hip_sample_with_multitalk(self, latents, prompt_emb_posi, prompt_emb_nega, 
         ctx_p, ctx_n = _stable_bf16(hip, ctx_p), _stable_bf16(hip, ctx_n)
     with torch.no_grad():
         return loop._sample_talk3(latents, ctx_p, ctx_n, audio_embed_tuple, audio_embed_tuple_null, float(cfg_scale["text"]), float(cfg_scale["audio"]),
-                                  self.scheduler.timesteps, lambda t: _step_delta_of(self.scheduler, t), progress_bar_cmd, cond)
+                                  self.scheduler.timesteps, lambda t: _step_delta_of(self.scheduler, t), progress_bar_cmd, cond,
+                                  tea=_talk_sampler_tea(tea_cache_posi, tea_cache_nega) if serves_tea else None)
 
 
 # ------------------------------------------------------------------------------------------------------

@@ -8,79 +8,110 @@
 // Rounding: the reference runs these ops as separate bf16 tensor ops; `rbf()` marks each point
 // where it materialises a bf16 tensor so results track it to within accumulation-order noise.
 #include "svi_common.h"
+#include <type_traits>
 
 #define ROWS_PER_BLOCK 4      // 4 waves / 256 threads per workgroup
+
+// A kernel is built for MAXC chunks per lane: 3 (up to 1536 columns, the 1.3B width), 10 (up to 5120, the 14B width) or 16 (up to 8192).
+// launch(std::integral_constant<int, MAXC>) instantiates and launches; the one place the widths are mapped.
+template <class F>
+static void with_maxc(int nchunk, F&& launch) {
+    if (nchunk <= 64 * 3) launch(std::integral_constant<int, 3>{});
+    else if (nchunk <= 64 * 10) launch(std::integral_constant<int, 10>{});
+    else launch(std::integral_constant<int, 16>{});
+}
+constexpr int RPW = 4;        // rows a wave of the multi-row kernels walks (they exist for rows of 3 and of 10 whole chunks per lane)
+
+// grid of the grid-stride 1-D kernels: 256 elements per workgroup, at most `cap` workgroups
+static dim3 grid_1d(int64_t n, int cap) { return dim3((unsigned)((n + 255) / 256 < cap ? (n + 255) / 256 : cap)); }
 
 // ------------------------------------------------------------------------------------------------
 // LayerNorm (no affine | affine) [+ modulate]:  out = ((x-mean)*rstd [*w+b]) [*(1+scale)+shift]
 // reference: nn.LayerNorm(eps=1e-6) + modulate(), models/wan_video_dit.py:150-151,331-333,358,370,372
+//
+// The row body.  ln_mod_kernel and add_ln_mod_skip_kernel both call ln_row_stats and ln_emit_chunk on a wave's row held as float v[MAXC][8] and the
+// project builds with -ffp-contract=off, so their results cannot diverge: a row has the same bits whichever of them wrote it.  ln_mod_rows_kernel keeps
+// the same statements written out (see there).
 // ------------------------------------------------------------------------------------------------
+// FULL: every lane holds MAXC whole chunks (no guards); otherwise chunk lane + 64 c exists while it is below nchunk.
+template <int MAXC, bool FULL>
+__device__ __forceinline__ void ln_row_stats(const float (&v)[MAXC][8], int lane, int nchunk, int dim, float eps, float& mean, float& rstd) {
+    float s = 0.f;
+#pragma unroll
+    for (int c = 0; c < MAXC; ++c)
+        if (FULL || lane + 64 * c < nchunk) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) s += v[c][j];
+        }
+    mean = wave_sum(s) / (float)dim;
+    float q = 0.f;
+#pragma unroll
+    for (int c = 0; c < MAXC; ++c)
+        if (FULL || lane + 64 * c < nchunk) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) { float d = v[c][j] - mean; q += d * d; }
+        }
+    rstd = rsqrtf(wave_sum(q) / (float)dim + eps);
+}
+
+// the affine and modulation vectors of one chunk (columns col .. col + 7); a part that is not asked for is left unset and never read
+struct LnVecs { bf16x8 w, b; f32x4 sc[2], sh[2]; };
+__device__ __forceinline__ LnVecs ln_load_vecs(bool affine, bool mod, const bf16* __restrict__ w, const bf16* __restrict__ b, const float* __restrict__ shift,
+                                               const float* __restrict__ scale1p, int col) {
+    LnVecs p;
+    if (affine) { p.w = ld_bf16x8(w + col); p.b = ld_bf16x8(b + col); }
+    if (mod) {
+        p.sc[0] = *reinterpret_cast<const f32x4*>(scale1p + col); p.sc[1] = *reinterpret_cast<const f32x4*>(scale1p + col + 4);
+        p.sh[0] = *reinterpret_cast<const f32x4*>(shift + col); p.sh[1] = *reinterpret_cast<const f32x4*>(shift + col + 4);
+    }
+    return p;
+}
+// affine / mod are compile-time constants in the kernels that are templated on them and wave-uniform flags in ln_mod_kernel
+__device__ __forceinline__ bf16x8 ln_emit_chunk(const float (&v)[8], float mean, float rstd, bool affine, bool mod, const LnVecs& p) {
+    bf16x8 o;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        float y = (v[j] - mean) * rstd;
+        if (affine) y = y * (float)p.w[j] + (float)p.b[j];
+        y = rbf(y);
+        if (mod) y = rbf(rbf(y * p.sc[j >> 2][j & 3]) + p.sh[j >> 2][j & 3]);
+        o[j] = (bf16)y;
+    }
+    return o;
+}
+
+// generic: one row per wave, any dim that is a multiple of 8
 template <int MAXC>
-__global__ __launch_bounds__(256) void ln_mod_kernel(const bf16* __restrict__ x, int ldx, bf16* __restrict__ out,
-                                                     int ldo, int rows, int dim, float eps,
-                                                     const bf16* __restrict__ w, const bf16* __restrict__ b,
-                                                     const float* __restrict__ shift,
-                                                     const float* __restrict__ scale1p) {
+__global__ __launch_bounds__(256) void ln_mod_kernel(const bf16* __restrict__ x, int ldx, bf16* __restrict__ out, int ldo, int rows, int dim, float eps,
+                                                     const bf16* __restrict__ w, const bf16* __restrict__ b, const float* __restrict__ shift, const float* __restrict__ scale1p) {
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6);
     if (row >= rows) return;
     const int nchunk = dim >> 3;
     const bf16* xr = x + (size_t)row * ldx;
     float v[MAXC][8];
-    float s = 0.f;
 #pragma unroll
     for (int c = 0; c < MAXC; ++c) {
         const int ci = lane + 64 * c;
-        if (ci < nchunk) {
-            bf16x8 t = ld_bf16x8(xr + ci * 8);
+        bf16x8 t = {};
+        if (ci < nchunk) t = ld_bf16x8(xr + ci * 8);
 #pragma unroll
-            for (int j = 0; j < 8; ++j) { v[c][j] = (float)t[j]; s += v[c][j]; }
-        } else {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) v[c][j] = 0.f;
-        }
+        for (int j = 0; j < 8; ++j) v[c][j] = (float)t[j];
     }
-    const float mean = wave_sum(s) / (float)dim;
-    float q = 0.f;
-#pragma unroll
-    for (int c = 0; c < MAXC; ++c) {
-        const int ci = lane + 64 * c;
-        if (ci < nchunk) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) { float d = v[c][j] - mean; q += d * d; }
-        }
-    }
-    const float rstd = rsqrtf(wave_sum(q) / (float)dim + eps);
+    float mean, rstd;
+    ln_row_stats<MAXC, false>(v, lane, nchunk, dim, eps, mean, rstd);
     bf16* orow = out + (size_t)row * ldo;
 #pragma unroll
     for (int c = 0; c < MAXC; ++c) {
         const int ci = lane + 64 * c;
-        if (ci < nchunk) {
-            const int col = ci * 8;
-            bf16x8 o;
-            bf16x8 wv, bv;
-            if (w) { wv = ld_bf16x8(w + col); bv = ld_bf16x8(b + col); }
-            f32x4 sc0, sc1, sh0, sh1;
-            if (scale1p) {
-                sc0 = *reinterpret_cast<const f32x4*>(scale1p + col); sc1 = *reinterpret_cast<const f32x4*>(scale1p + col + 4);
-                sh0 = *reinterpret_cast<const f32x4*>(shift + col); sh1 = *reinterpret_cast<const f32x4*>(shift + col + 4);
-            }
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                float y = (v[c][j] - mean) * rstd;
-                if (w) y = y * (float)wv[j] + (float)bv[j];
-                y = rbf(y);
-                if (scale1p) y = rbf(rbf(y * (j < 4 ? sc0[j & 3] : sc1[j & 3])) + (j < 4 ? sh0[j & 3] : sh1[j & 3]));
-                o[j] = (bf16)y;
-            }
-            st_bf16x8(orow + col, o);
-        }
+        if (ci < nchunk) st_bf16x8(orow + ci * 8, ln_emit_chunk(v[c], mean, rstd, w != nullptr, scale1p != nullptr, ln_load_vecs(w != nullptr, scale1p != nullptr, w, b, shift, scale1p, ci * 8)));
     }
 }
 
-// The same arithmetic for rows of whole chunks (dim = 512 MAXC): a wave walks RPW consecutive rows with row i + 1 requested before row i is
-// worked on; for MAXC <= 3 (the 1.3B width) the modulation / affine vectors stay in registers instead of being reloaded for every row.
-// Bit-identical to ln_mod_kernel.
+// Rows of whole chunks (dim = 512 MAXC): a wave walks RPW consecutive rows with row i + 1 requested before row i is worked on; for MAXC <= 3 (the 1.3B
+// width) the modulation / affine vectors stay in registers instead of being reloaded for every row.  The arithmetic is the row body's, written out:
+// built on ln_row_stats / ln_emit_chunk the compiler schedules this kernel differently and the step's LayerNorm time rose by 0.7 % (5.64 -> 5.68 ms,
+// profiles/row_body_ab.txt).  tests/test_gpu_row_kernels.py holds it to ln_mod_kernel bit for bit.
 template <int MAXC, int RPW, bool AFFINE, bool MOD>
 __global__ __launch_bounds__(256) void ln_mod_rows_kernel(const bf16* __restrict__ x, int ldx, bf16* __restrict__ out, int ldo, int rows, int dim, float eps,
                                                           const bf16* __restrict__ w, const bf16* __restrict__ b, const float* __restrict__ shift,
@@ -157,8 +188,7 @@ __global__ __launch_bounds__(256) void ln_mod_rows_kernel(const bf16* __restrict
 }
 
 svi_status svi_launch_ln_mod(const bf16* x, int ldx, bf16* out, int ldo, int rows, int dim, float eps,
-                             const bf16* w, const bf16* b, const float* shift, const float* scale1p,
-                             hipStream_t st) {
+                             const bf16* w, const bf16* b, const float* shift, const float* scale1p, hipStream_t st) {
     SVI_REQUIRE(dim % 8 == 0 && ldx % 8 == 0 && ldo % 8 == 0, "layernorm: dim/ld must be multiples of 8 (dim=%d)", dim);
     SVI_REQUIRE(dim <= 8192, "layernorm: dim %d > 8192 unsupported", dim);
     SVI_REQUIRE((w == nullptr) == (b == nullptr), "layernorm: affine weight and bias must come together");
@@ -168,27 +198,17 @@ svi_status svi_launch_ln_mod(const bf16* x, int ldx, bf16* out, int ldo, int row
     const int nchunk = dim / 8;
     // the DiT's widths (whole chunks per lane) and norm kinds (modulated without affine: norm1 / norm2; affine without modulation: norm3): the
     // multi-row kernel.  The modulation vectors must be 16-byte aligned for its vector loads (the DiT's are).
-    if ((nchunk == 64 * 3 || nchunk == 64 * 10) && svi_switches().rms_rows && ((w != nullptr) != (scale1p != nullptr)) &&
-        ((((uintptr_t)shift | (uintptr_t)scale1p) & 15) == 0)) {
-        constexpr int RPW = 4;
-        dim3 grid_r((rows + ROWS_PER_BLOCK * RPW - 1) / (ROWS_PER_BLOCK * RPW));
-#define SVI_LN_ROWS(MAXC)                                                                                                                 \
-        do {                                                                                                                              \
-            if (w) hipLaunchKernelGGL((ln_mod_rows_kernel<MAXC, RPW, true, false>), grid_r, block, 0, st, x, ldx, out, ldo, rows, dim, eps, w, b, shift, scale1p);   \
-            else hipLaunchKernelGGL((ln_mod_rows_kernel<MAXC, RPW, false, true>), grid_r, block, 0, st, x, ldx, out, ldo, rows, dim, eps, w, b, shift, scale1p);   \
-        } while (0)
-        if (nchunk == 64 * 3) SVI_LN_ROWS(3);
-        else SVI_LN_ROWS(10);
-#undef SVI_LN_ROWS
-        SVI_LAUNCH_CHECK();
-        return SVI_OK;
-    }
-    if (nchunk <= 64 * 3)
-        hipLaunchKernelGGL(ln_mod_kernel<3>, grid, block, 0, st, x, ldx, out, ldo, rows, dim, eps, w, b, shift, scale1p);
-    else if (nchunk <= 64 * 10)
-        hipLaunchKernelGGL(ln_mod_kernel<10>, grid, block, 0, st, x, ldx, out, ldo, rows, dim, eps, w, b, shift, scale1p);
-    else
-        hipLaunchKernelGGL(ln_mod_kernel<16>, grid, block, 0, st, x, ldx, out, ldo, rows, dim, eps, w, b, shift, scale1p);
+    const bool multi_row = (nchunk == 64 * 3 || nchunk == 64 * 10) && svi_switches().rms_rows && ((w != nullptr) != (scale1p != nullptr)) &&
+                           ((((uintptr_t)shift | (uintptr_t)scale1p) & 15) == 0);
+    const dim3 grid_r((rows + ROWS_PER_BLOCK * RPW - 1) / (ROWS_PER_BLOCK * RPW));
+    with_maxc(nchunk, [&](auto mc) {
+        constexpr int MAXC = decltype(mc)::value;
+        if constexpr (MAXC <= 10) {
+            if (multi_row && w) { hipLaunchKernelGGL((ln_mod_rows_kernel<MAXC, RPW, true, false>), grid_r, block, 0, st, x, ldx, out, ldo, rows, dim, eps, w, b, shift, scale1p); return; }
+            if (multi_row) { hipLaunchKernelGGL((ln_mod_rows_kernel<MAXC, RPW, false, true>), grid_r, block, 0, st, x, ldx, out, ldo, rows, dim, eps, w, b, shift, scale1p); return; }
+        }
+        hipLaunchKernelGGL(ln_mod_kernel<MAXC>, grid, block, 0, st, x, ldx, out, ldo, rows, dim, eps, w, b, shift, scale1p);
+    });
     SVI_LAUNCH_CHECK();
     return SVI_OK;
 }
@@ -200,12 +220,50 @@ svi_status svi_launch_ln_mod(const bf16* x, int ldx, bf16* out, int ldo, int row
 // here cos/sin come from a host-built fp64->fp32 table and the 2x2 rotate runs in fp32 — the result
 // is rounded to bf16 either way (difference <= 1 bf16 ulp on rounding ties only).
 // ------------------------------------------------------------------------------------------------
+// The row body.  rmsnorm_rope_kernel and rmsnorm_rope_rows_kernel both call rms_row_rs and rms_emit_chunk, so their results cannot diverge (FULL as above).
+template <int MAXC, bool FULL>
+__device__ __forceinline__ float rms_row_rs(const float (&v)[MAXC][8], int lane, int nchunk, int dim, float eps) {
+    float ss = 0.f;
+#pragma unroll
+    for (int c = 0; c < MAXC; ++c)
+        if (FULL || lane + 64 * c < nchunk) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) ss += v[c][j] * v[c][j];
+        }
+    return rsqrtf(wave_sum(ss) / (float)dim + eps);
+}
+// one chunk: normalise, gain, [rotate its four complex pairs by (cx[p], sy[p]) = (cos, sin)], scale
+__device__ __forceinline__ bf16x8 rms_emit_chunk(const float (&v)[8], float rs, bf16x8 gain, bool rope, const float (&cx)[4], const float (&sy)[4], float out_scale) {
+    float y[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) y[j] = rbf(rbf(v[j] * rs) * (float)gain[j]);
+    bf16x8 o;
+    if (rope) {
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            const float a = y[2 * p], bq = y[2 * p + 1];
+            o[2 * p] = (bf16)((a * cx[p] - bq * sy[p]) * out_scale);
+            o[2 * p + 1] = (bf16)((a * sy[p] + bq * cx[p]) * out_scale);
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) o[j] = (bf16)(y[j] * out_scale);
+    }
+    return o;
+}
+// the four (cos, sin) pairs at tt[0 .. 3] of a token's table row
+__device__ __forceinline__ void rope_pairs_of(const float2* tt, float (&cx)[4], float (&sy)[4]) {
+    const f32x4 t01 = *reinterpret_cast<const f32x4*>(tt), t23 = *reinterpret_cast<const f32x4*>(tt + 2);
+    cx[0] = t01[0]; cx[1] = t01[2]; cx[2] = t23[0]; cx[3] = t23[2];
+    sy[0] = t01[1]; sy[1] = t01[3]; sy[2] = t23[1]; sy[3] = t23[3];
+}
+
 // blockIdx.y selects one of up to two [rows, dim] operands that sit side by side in a row (q | k of the DiT's QK buffer): operand
 // p starts at column p * dim and has its own weight and output scale — one launch normalises both.
+// generic: one row per wave, any dim that is a multiple of 8; RoPE from the per-token table or the three axis tables; in place or to SviScatter
 template <int MAXC, bool SCATTER>
-__global__ __launch_bounds__(256) void rmsnorm_rope_kernel(bf16* __restrict__ x, int ld, int rows, int dim,
-                                                           const bf16* __restrict__ weight, const bf16* __restrict__ weight1, float eps, int use_rope,
-                                                           SviRope r, float out_scale, float out_scale1, SviScatter sc) {
+__global__ __launch_bounds__(256) void rmsnorm_rope_kernel(bf16* __restrict__ x, int ld, int rows, int dim, const bf16* __restrict__ weight,
+                                                           const bf16* __restrict__ weight1, float eps, int use_rope, SviRope r, float out_scale, float out_scale1, SviScatter sc) {
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6);
     if (row >= rows) return;
@@ -213,17 +271,16 @@ __global__ __launch_bounds__(256) void rmsnorm_rope_kernel(bf16* __restrict__ x,
     bf16* xr = x + (size_t)row * ld + (size_t)blockIdx.y * dim;
     if (blockIdx.y) { weight = weight1; out_scale = out_scale1; }
     float v[MAXC][8];
-    float ss = 0.f;
 #pragma unroll
     for (int c = 0; c < MAXC; ++c) {
         const int ci = lane + 64 * c;
         if (ci < nchunk) {
             bf16x8 t = ld_bf16x8(xr + ci * 8);
 #pragma unroll
-            for (int j = 0; j < 8; ++j) { v[c][j] = (float)t[j]; ss += v[c][j] * v[c][j]; }
+            for (int j = 0; j < 8; ++j) v[c][j] = (float)t[j];
         }
     }
-    const float rs = rsqrtf(wave_sum(ss) / (float)dim + eps);
+    const float rs = rms_row_rs<MAXC, false>(v, lane, nchunk, dim, eps);
     int pf = 0, ph = 0, pw = 0;
     const float2* tt = nullptr;                  // this token's 64 pairs, when the caller gathered them (SviRope::tab_tok)
     if (use_rope) {
@@ -242,34 +299,23 @@ __global__ __launch_bounds__(256) void rmsnorm_rope_kernel(bf16* __restrict__ x,
         const int ci = lane + 64 * c;
         if (ci < nchunk) {
             const int col = ci * 8;
-            bf16x8 wv = ld_bf16x8(weight + col);
-            float y[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) y[j] = rbf(rbf(v[c][j] * rs) * (float)wv[j]);
-            bf16x8 o;
+            float cx[4], sy[4];
             if (use_rope) {
                 const int pair0 = (col & 127) >> 1;            // complex-pair index inside the head
-                f32x4 t01 = {0.f, 0.f, 0.f, 0.f}, t23 = t01;
-                if (tt) {
-                    t01 = *reinterpret_cast<const f32x4*>(tt + pair0);
-                    t23 = *reinterpret_cast<const f32x4*>(tt + pair0 + 2);
-                }
+                if (tt) rope_pairs_of(tt + pair0, cx, sy);
+                else {
 #pragma unroll
-                for (int p = 0; p < 4; ++p) {
-                    const int pi = pair0 + p;
-                    float2 cs;
-                    if (tt) cs = p == 0 ? make_float2(t01[0], t01[1]) : p == 1 ? make_float2(t01[2], t01[3]) : p == 2 ? make_float2(t23[0], t23[1]) : make_float2(t23[2], t23[3]);
-                    else if (pi < r.npf) cs = r.tab_f[pf * r.npf + pi];
-                    else if (pi < r.npf + r.nph) cs = r.tab_h[ph * r.nph + (pi - r.npf)];
-                    else cs = r.tab_w[pw * r.npw + (pi - r.npf - r.nph)];
-                    const float a = y[2 * p], bq = y[2 * p + 1];
-                    o[2 * p] = (bf16)((a * cs.x - bq * cs.y) * out_scale);
-                    o[2 * p + 1] = (bf16)((a * cs.y + bq * cs.x) * out_scale);
+                    for (int p = 0; p < 4; ++p) {
+                        const int pi = pair0 + p;
+                        float2 cs;
+                        if (pi < r.npf) cs = r.tab_f[pf * r.npf + pi];
+                        else if (pi < r.npf + r.nph) cs = r.tab_h[ph * r.nph + (pi - r.npf)];
+                        else cs = r.tab_w[pw * r.npw + (pi - r.npf - r.nph)];
+                        cx[p] = cs.x; sy[p] = cs.y;
+                    }
                 }
-            } else {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) o[j] = (bf16)(y[j] * out_scale);
             }
+            const bf16x8 o = rms_emit_chunk(v[c], rs, ld_bf16x8(weight + col), use_rope != 0, cx, sy, out_scale);
             if constexpr (SCATTER) {
                 const int j = col / sc.Dp, cl = col - j * sc.Dp, gq = cl / sc.Dg, cg = cl - gq * sc.Dg;
                 bf16* ob = blockIdx.y ? sc.out1 : sc.out0;
@@ -283,9 +329,9 @@ __global__ __launch_bounds__(256) void rmsnorm_rope_kernel(bf16* __restrict__ x,
     }
 }
 
-// The same arithmetic for the shapes the DiT runs (every lane holds MAXC whole chunks: dim = 512 MAXC; RoPE from the per-token table or none;
-// in place): a wave walks RPW consecutive rows, requests row i + 1 before it works on row i, and keeps the gain vector in registers — the
-// generic kernel above reloads and unpacks it for every row and has one row in flight per wave.  Bit-identical results.
+// The shapes the DiT runs (every lane holds MAXC whole chunks: dim = 512 MAXC; RoPE from the per-token table or none; in place): a wave walks RPW
+// consecutive rows, requests row i + 1 before it works on row i, and keeps the gain vector in registers — the generic kernel above reloads and unpacks
+// it for every row and has one row in flight per wave.
 // Q8 (opt-in fp8 QK^T attention): the result rows leave as MX e4m3 bytes + E8M0 block scales (operand blockIdx.y -> q8o.q8 / q8o.k8) instead of bf16 —
 // a lane's 8 channels are a quarter of a 32-channel block and 16 lanes one head: the quantiser's own lane layout (mx8_quant8), so the bits are those
 // svi_launch_mx8_quantize makes of the bf16 rows this kernel would have written.
@@ -311,12 +357,11 @@ __global__ __launch_bounds__(256) void rmsnorm_rope_rows_kernel(bf16* __restrict
             for (int c = 0; c < MAXC; ++c) nxt[c] = ld_bf16x8(xb + (size_t)(row + 1) * ld + (lane + 64 * c) * 8);
         }
         float v[MAXC][8];
-        float ss = 0.f;
 #pragma unroll
         for (int c = 0; c < MAXC; ++c)
 #pragma unroll
-            for (int j = 0; j < 8; ++j) { v[c][j] = (float)cur[c][j]; ss += v[c][j] * v[c][j]; }
-        const float rs = rsqrtf(wave_sum(ss) / (float)dim + eps);
+            for (int j = 0; j < 8; ++j) v[c][j] = (float)cur[c][j];
+        const float rs = rms_row_rs<MAXC, true>(v, lane, MAXC * 64, dim, eps);
         const float2* tt = nullptr;
         if (ROPE) {
             int tok = row;
@@ -328,24 +373,9 @@ __global__ __launch_bounds__(256) void rmsnorm_rope_rows_kernel(bf16* __restrict
 #pragma unroll
         for (int c = 0; c < MAXC; ++c) {
             const int col = (lane + 64 * c) * 8;
-            float y[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) y[j] = rbf(rbf(v[c][j] * rs) * (float)wv[c][j]);
-            bf16x8 o;
-            if (ROPE) {
-                const int pair0 = (col & 127) >> 1;
-                const f32x4 t01 = *reinterpret_cast<const f32x4*>(tt + pair0), t23 = *reinterpret_cast<const f32x4*>(tt + pair0 + 2);
-                const float cx[4] = {t01[0], t01[2], t23[0], t23[2]}, sy[4] = {t01[1], t01[3], t23[1], t23[3]};
-#pragma unroll
-                for (int p = 0; p < 4; ++p) {
-                    const float a = y[2 * p], bq = y[2 * p + 1];
-                    o[2 * p] = (bf16)((a * cx[p] - bq * sy[p]) * out_scale);
-                    o[2 * p + 1] = (bf16)((a * sy[p] + bq * cx[p]) * out_scale);
-                }
-            } else {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) o[j] = (bf16)(y[j] * out_scale);
-            }
+            float cx[4], sy[4];
+            if (ROPE) rope_pairs_of(tt + ((col & 127) >> 1), cx, sy);
+            const bf16x8 o = rms_emit_chunk(v[c], rs, wv[c], ROPE, cx, sy, out_scale);
             if constexpr (Q8) {
                 float vq[8];
 #pragma unroll
@@ -395,10 +425,11 @@ svi_status svi_launch_rmsnorm_rope2_q8(bf16* x, int ld, int rows, int dim, const
     SVI_REQUIRE(rope->npf + rope->nph + rope->npw == 64 && rope->row0 >= 0 && (rope->period > 0 ? (rope->row0 + rope->period <= rope->f * rope->h * rope->w && rows % rope->period == 0) : rope->row0 + rows <= rope->f * rope->h * rope->w),
                 "rope grid %dx%dx%d does not cover rows [%d, %d)", rope->f, rope->h, rope->w, rope->row0, rope->row0 + rows);
     if (rows <= 0) return SVI_OK;
-    constexpr int RPW = 4;
     dim3 grid_r((rows + ROWS_PER_BLOCK * RPW - 1) / (ROWS_PER_BLOCK * RPW), 2), block(256);
-    if (dim == 512 * 3) hipLaunchKernelGGL((rmsnorm_rope_rows_kernel<3, RPW, true, true>), grid_r, block, 0, st, x, ld, rows, dim, weight, weight1, eps, *rope, out_scale, out_scale1, out);
-    else hipLaunchKernelGGL((rmsnorm_rope_rows_kernel<10, RPW, true, true>), grid_r, block, 0, st, x, ld, rows, dim, weight, weight1, eps, *rope, out_scale, out_scale1, out);
+    with_maxc(dim / 8, [&](auto mc) {
+        constexpr int MAXC = decltype(mc)::value;
+        if constexpr (MAXC <= 10) hipLaunchKernelGGL((rmsnorm_rope_rows_kernel<MAXC, RPW, true, true>), grid_r, block, 0, st, x, ld, rows, dim, weight, weight1, eps, *rope, out_scale, out_scale1, out);
+    });
     SVI_LAUNCH_CHECK();
     return SVI_OK;
 }
@@ -433,30 +464,18 @@ svi_status svi_launch_rmsnorm_rope2(bf16* x, int ld, int rows, int dim, const bf
         SVI_REQUIRE(sc.rows_per_sample == 0 || (sc.rows_per_sample > 0 && rows % sc.rows_per_sample == 0),
                     "rmsnorm: %d rows are not whole samples of %d rows", rows, sc.rows_per_sample);
     }
-#define SVI_RMS_LAUNCH(MAXC)                                                                                                             \
-    do {                                                                                                                                 \
-        if (scatter) hipLaunchKernelGGL((rmsnorm_rope_kernel<MAXC, true>), grid, block, 0, st, x, ld, rows, dim, weight, weight1, eps, use, r, out_scale, out_scale1, sc);  \
-        else hipLaunchKernelGGL((rmsnorm_rope_kernel<MAXC, false>), grid, block, 0, st, x, ld, rows, dim, weight, weight1, eps, use, r, out_scale, out_scale1, sc);        \
-    } while (0)
     // the DiT's shapes (in place, whole chunks per lane, per-token RoPE table or no RoPE): the multi-row kernel
-    if (!scatter && (nchunk == 64 * 3 || nchunk == 64 * 10) && (!rope || r.tab_tok) && svi_switches().rms_rows) {
-        constexpr int RPW = 4;
-        dim3 grid_r((rows + ROWS_PER_BLOCK * RPW - 1) / (ROWS_PER_BLOCK * RPW), weight1 ? 2 : 1);
-#define SVI_RMS_ROWS(MAXC)                                                                                                               \
-        do {                                                                                                                             \
-            if (rope) hipLaunchKernelGGL((rmsnorm_rope_rows_kernel<MAXC, RPW, true>), grid_r, block, 0, st, x, ld, rows, dim, weight, weight1, eps, r, out_scale, out_scale1);   \
-            else hipLaunchKernelGGL((rmsnorm_rope_rows_kernel<MAXC, RPW, false>), grid_r, block, 0, st, x, ld, rows, dim, weight, weight1, eps, r, out_scale, out_scale1);       \
-        } while (0)
-        if (nchunk == 64 * 3) SVI_RMS_ROWS(3);
-        else SVI_RMS_ROWS(10);
-#undef SVI_RMS_ROWS
-        SVI_LAUNCH_CHECK();
-        return SVI_OK;
-    }
-    if (nchunk <= 64 * 3) SVI_RMS_LAUNCH(3);
-    else if (nchunk <= 64 * 10) SVI_RMS_LAUNCH(10);
-    else SVI_RMS_LAUNCH(16);
-#undef SVI_RMS_LAUNCH
+    const bool multi_row = !scatter && (nchunk == 64 * 3 || nchunk == 64 * 10) && (!rope || r.tab_tok) && svi_switches().rms_rows;
+    const dim3 grid_r((rows + ROWS_PER_BLOCK * RPW - 1) / (ROWS_PER_BLOCK * RPW), weight1 ? 2 : 1);
+    with_maxc(nchunk, [&](auto mc) {
+        constexpr int MAXC = decltype(mc)::value;
+        if constexpr (MAXC <= 10) {
+            if (multi_row && rope) { hipLaunchKernelGGL((rmsnorm_rope_rows_kernel<MAXC, RPW, true>), grid_r, block, 0, st, x, ld, rows, dim, weight, weight1, eps, r, out_scale, out_scale1); return; }
+            if (multi_row) { hipLaunchKernelGGL((rmsnorm_rope_rows_kernel<MAXC, RPW, false>), grid_r, block, 0, st, x, ld, rows, dim, weight, weight1, eps, r, out_scale, out_scale1); return; }
+        }
+        if (scatter) hipLaunchKernelGGL((rmsnorm_rope_kernel<MAXC, true>), grid, block, 0, st, x, ld, rows, dim, weight, weight1, eps, use, r, out_scale, out_scale1, sc);
+        else hipLaunchKernelGGL((rmsnorm_rope_kernel<MAXC, false>), grid, block, 0, st, x, ld, rows, dim, weight, weight1, eps, use, r, out_scale, out_scale1, sc);
+    });
     SVI_LAUNCH_CHECK();
     return SVI_OK;
 }
@@ -512,9 +531,7 @@ __global__ __launch_bounds__(256) void cfg_step_kernel(bf16* __restrict__ lat, c
 svi_status svi_launch_cfg_step(bf16* lat, const bf16* cond, const bf16* uncond, int64_t n, float s, float dsigma,
                                hipStream_t st) {
     if (n <= 0) return SVI_OK;
-    int blocks = (int)((n + 255) / 256);
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(cfg_step_kernel, dim3(blocks), dim3(256), 0, st, lat, cond, uncond, n, s, dsigma);
+    hipLaunchKernelGGL(cfg_step_kernel, grid_1d(n, 2048), dim3(256), 0, st, lat, cond, uncond, n, s, dsigma);
     SVI_LAUNCH_CHECK();
     return SVI_OK;
 }
@@ -534,9 +551,7 @@ __global__ __launch_bounds__(256) void sub_bf16_kernel(bf16* __restrict__ out, c
 
 svi_status svi_launch_sub_bf16(bf16* out, const bf16* a, const bf16* b, int64_t n, hipStream_t st) {
     if (n <= 0) return SVI_OK;
-    int blocks = (int)((n + 255) / 256);
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(sub_bf16_kernel, dim3(blocks), dim3(256), 0, st, out, a, b, n);
+    hipLaunchKernelGGL(sub_bf16_kernel, grid_1d(n, 4096), dim3(256), 0, st, out, a, b, n);
     SVI_LAUNCH_CHECK();
     return SVI_OK;
 }
@@ -561,142 +576,48 @@ svi_status svi_launch_sub_sum_bf16(bf16* out, const bf16* a, const bf16* b, cons
     SVI_REQUIRE(n % 8 == 0 && (((uintptr_t)out | (uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0, "sub_sum: operands must be 16-byte aligned, n a multiple of 8");
     if (n <= 0) return SVI_OK;
     const int64_t n8 = n / 8;
-    int blocks = (int)((n8 + 255) / 256);
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(sub_sum_bf16_kernel, dim3(blocks), dim3(256), 0, st, out, a, b, c, n8);
+    hipLaunchKernelGGL(sub_sum_bf16_kernel, grid_1d(n8, 2048), dim3(256), 0, st, out, a, b, c, n8);
     SVI_LAUNCH_CHECK();
     return SVI_OK;
 }
 
 svi_status svi_launch_add_bf16(bf16* a, const bf16* b, int64_t n, hipStream_t st) {
     if (n <= 0) return SVI_OK;
-    int blocks = (int)((n + 255) / 256);
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(add_bf16_kernel, dim3(blocks), dim3(256), 0, st, a, b, n);
+    hipLaunchKernelGGL(add_bf16_kernel, grid_1d(n, 4096), dim3(256), 0, st, a, b, n);
     SVI_LAUNCH_CHECK();
     return SVI_OK;
 }
 
 // ------------------------------------------------------------------------------------------------
-// TeaCache skip step of a CFG pair (pipelines/svi_video.py:68-70, then the head's norm, models/wan_video_dit.py:401-404): both branches see the
-// same patch-embedded row of X and differ in their cached residual only.  One wave reads the row of X once and, per branch, the matching residual
-// row, forms bf16(x + residual) — add_bf16_kernel's rounding point — and writes that branch's LayerNorm + modulate row: X is left as it is, and the
-// add_bf16 pass over X and the separate LayerNorm launch per branch are gone (three row reads and two row writes instead of six and four).
-// The statistics and the output arithmetic are ln_mod_kernel's, statement for statement (sum over the lane's chunks in order, wave_sum, the same
-// rbf() points), so each output row has the bits of add_bf16 followed by svi_launch_ln_mod (either of its kernels: they agree bit for bit).
-// res_b / out_b may be null: one branch only.
-template <int MAXC>
-__global__ __launch_bounds__(256) void add_ln_mod_pair_kernel(const bf16* __restrict__ x, const bf16* __restrict__ res_a, const bf16* __restrict__ res_b,
-                                                              bf16* __restrict__ out_a, bf16* __restrict__ out_b, int rows, int dim, float eps,
-                                                              const float* __restrict__ shift, const float* __restrict__ scale1p) {
-    const int lane = threadIdx.x & 63;
-    const int row = blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const int nchunk = dim >> 3;
-    const size_t roff = (size_t)row * dim;
-    bf16x8 xv[MAXC];
-#pragma unroll
-    for (int c = 0; c < MAXC; ++c) {
-        const int ci = lane + 64 * c;
-        if (ci < nchunk) xv[c] = ld_bf16x8(x + roff + ci * 8);
-    }
-#pragma unroll
-    for (int br = 0; br < 2; ++br) {
-        const bf16* res = br ? res_b : res_a;
-        bf16* out = br ? out_b : out_a;
-        if (!res) continue;                              // uniform over the grid
-        float v[MAXC][8];
-        float s = 0.f;
-#pragma unroll
-        for (int c = 0; c < MAXC; ++c) {
-            const int ci = lane + 64 * c;
-            if (ci < nchunk) {
-                const bf16x8 r = ld_bf16x8(res + roff + ci * 8);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) { v[c][j] = (float)(bf16)((float)xv[c][j] + (float)r[j]); s += v[c][j]; }
-            } else {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) v[c][j] = 0.f;
-            }
-        }
-        const float mean = wave_sum(s) / (float)dim;
-        float q = 0.f;
-#pragma unroll
-        for (int c = 0; c < MAXC; ++c) {
-            const int ci = lane + 64 * c;
-            if (ci < nchunk) {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) { float d = v[c][j] - mean; q += d * d; }
-            }
-        }
-        const float rstd = rsqrtf(wave_sum(q) / (float)dim + eps);
-#pragma unroll
-        for (int c = 0; c < MAXC; ++c) {
-            const int ci = lane + 64 * c;
-            if (ci < nchunk) {
-                const int col = ci * 8;
-                const f32x4 sc0 = *reinterpret_cast<const f32x4*>(scale1p + col), sc1 = *reinterpret_cast<const f32x4*>(scale1p + col + 4);
-                const f32x4 sh0 = *reinterpret_cast<const f32x4*>(shift + col), sh1 = *reinterpret_cast<const f32x4*>(shift + col + 4);
-                bf16x8 o;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    float y = rbf((v[c][j] - mean) * rstd);
-                    y = rbf(rbf(y * (j < 4 ? sc0[j & 3] : sc1[j & 3])) + (j < 4 ? sh0[j & 3] : sh1[j & 3]));
-                    o[j] = (bf16)y;
-                }
-                st_bf16x8(out + roff + col, o);
-            }
-        }
-    }
-}
-
-// x, res_*, out_*: dense [rows, dim] bf16, 16-byte aligned; out_a / out_b are written, x and the residuals only read.
-svi_status svi_launch_add_ln_mod_pair(const bf16* x, const bf16* res_a, const bf16* res_b, bf16* out_a, bf16* out_b, int rows, int dim, float eps,
-                                      const float* shift, const float* scale1p, hipStream_t st) {
-    SVI_REQUIRE(x && res_a && out_a && shift && scale1p && (res_b == nullptr) == (out_b == nullptr), "add + layernorm: null operand");
-    SVI_REQUIRE(dim % 8 == 0 && dim <= 8192, "add + layernorm: dim %d must be a multiple of 8, at most 8192", dim);
-    SVI_REQUIRE((((uintptr_t)x | (uintptr_t)res_a | (uintptr_t)res_b | (uintptr_t)out_a | (uintptr_t)out_b | (uintptr_t)shift | (uintptr_t)scale1p) & 15) == 0,
-                "add + layernorm: operands must be 16-byte aligned");
-    if (rows <= 0) return SVI_OK;
-    dim3 grid((rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK), block(256);
-    const int nchunk = dim / 8;
-    if (nchunk <= 64 * 3)
-        hipLaunchKernelGGL(add_ln_mod_pair_kernel<3>, grid, block, 0, st, x, res_a, res_b, out_a, out_b, rows, dim, eps, shift, scale1p);
-    else if (nchunk <= 64 * 10)
-        hipLaunchKernelGGL(add_ln_mod_pair_kernel<10>, grid, block, 0, st, x, res_a, res_b, out_a, out_b, rows, dim, eps, shift, scale1p);
-    else
-        hipLaunchKernelGGL(add_ln_mod_pair_kernel<16>, grid, block, 0, st, x, res_a, res_b, out_a, out_b, rows, dim, eps, shift, scale1p);
-    SVI_LAUNCH_CHECK();
-    return SVI_OK;
-}
-
+// TeaCache skip step (pipelines/svi_video.py:68-70, then the head's norm, models/wan_video_dit.py:401-404): the branches of a guidance step see the same
+// patch-embedded row of X and differ in their cached residual — and, in the talk variant (svi_video_talk.py:448-466), in whether add_condition was added
+// to X first: cond and drop-text have it, uncond has not.  One wave reads the row of X once, the add_condition row once where a served branch has one,
+// and per served branch its residual row; it forms bf16(x_k + residual_k) — add_bf16_kernel's rounding point, as for x + add_condition — and writes that
+// branch's LayerNorm + modulate row through the row body above: each output row has the bits of add_bf16 (+ add_bf16) followed by svi_launch_ln_mod.
+// X is left as it is; the add_bf16 pass over X and the LayerNorm launch per branch are gone (a CFG pair: three row reads and two row writes, not six and
+// four).  A branch with res[k] == nullptr is not served.  NBR: 2 (a CFG pair) or 3 (the talk variant's cond, uncond, drop-text); ADDC: an add_condition
+// row is read (without it the x + add_condition registers do not exist).
 // ------------------------------------------------------------------------------------------------
-// TeaCache skip step of the talk variant (svi_video_talk.py:448-466): the three guidance branches see the same patch-embedded row of X; cond and drop-text
-// have add_condition added to it first (add_bf16_kernel's rounding point), uncond has not.  One wave reads the row of X once, the add_condition row once
-// where a skipping branch has one, and per skipping branch its residual row; it forms bf16(x_k + residual_k) and writes that branch's LayerNorm + modulate
-// row.  Statistics and output arithmetic are ln_mod_kernel's, statement for statement, as in add_ln_mod_pair_kernel: each output row has the bits of
-// add_bf16 (+ add_bf16) followed by svi_launch_ln_mod.  A branch with res[k] == nullptr is not served (it runs its blocks, or shares another's row).
-struct SviTalk3Skip {
-    const bf16* res[3];          // cond, uncond, drop-text: the residual rows of a skipping branch, nullptr otherwise
+struct SviSkipRows {
+    const bf16* res[3];          // the residual rows of a served branch, nullptr otherwise
     bf16* out[3];                // that branch's LayerNorm + modulate rows
     int addc[3];                 // the branch's embedded input has add_condition added
 };
-template <int MAXC>
-__global__ __launch_bounds__(256) void add_ln_mod_talk3_kernel(const bf16* __restrict__ x, const bf16* __restrict__ addc, SviTalk3Skip p, int rows, int dim,
-                                                               float eps, const float* __restrict__ shift, const float* __restrict__ scale1p) {
+template <int MAXC, int NBR, bool ADDC>
+__global__ __launch_bounds__(256) void add_ln_mod_skip_kernel(const bf16* __restrict__ x, const bf16* __restrict__ addc, SviSkipRows p, int rows, int dim,
+                                                              float eps, const float* __restrict__ shift, const float* __restrict__ scale1p) {
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6);
     if (row >= rows) return;
     const int nchunk = dim >> 3;
     const size_t roff = (size_t)row * dim;
-    bf16x8 xv[MAXC], xa[MAXC];          // the row of X, and bf16(x + add_condition)
+    bf16x8 xv[MAXC], xa[ADDC ? MAXC : 1];          // the row of X, and bf16(x + add_condition)
 #pragma unroll
     for (int c = 0; c < MAXC; ++c) {
         const int ci = lane + 64 * c;
         if (ci < nchunk) {
             xv[c] = ld_bf16x8(x + roff + ci * 8);
-            xa[c] = xv[c];
-            if (addc) {                                  // uniform over the grid
+            if constexpr (ADDC) {
                 const bf16x8 a = ld_bf16x8(addc + roff + ci * 8);
 #pragma unroll
                 for (int j = 0; j < 8; ++j) xa[c][j] = (bf16)((float)xv[c][j] + (float)a[j]);
@@ -704,63 +625,68 @@ __global__ __launch_bounds__(256) void add_ln_mod_talk3_kernel(const bf16* __res
         }
     }
 #pragma unroll
-    for (int br = 0; br < 3; ++br) {
+    for (int br = 0; br < NBR; ++br) {
         const bf16* res = p.res[br];
-        bf16* out = p.out[br];
         if (!res) continue;                              // uniform over the grid
-        const bool with_addc = p.addc[br] != 0;
         float v[MAXC][8];
-        float s = 0.f;
 #pragma unroll
         for (int c = 0; c < MAXC; ++c) {
             const int ci = lane + 64 * c;
             if (ci < nchunk) {
                 const bf16x8 r = ld_bf16x8(res + roff + ci * 8);
+                bf16x8 xin = xv[c];
+                if constexpr (ADDC) { if (p.addc[br]) xin = xa[c]; }
 #pragma unroll
-                for (int j = 0; j < 8; ++j) { v[c][j] = (float)(bf16)((float)(with_addc ? xa[c][j] : xv[c][j]) + (float)r[j]); s += v[c][j]; }
+                for (int j = 0; j < 8; ++j) v[c][j] = (float)(bf16)((float)xin[j] + (float)r[j]);
             } else {
 #pragma unroll
                 for (int j = 0; j < 8; ++j) v[c][j] = 0.f;
             }
         }
-        const float mean = wave_sum(s) / (float)dim;
-        float q = 0.f;
+        float mean, rstd;
+        ln_row_stats<MAXC, false>(v, lane, nchunk, dim, eps, mean, rstd);
 #pragma unroll
         for (int c = 0; c < MAXC; ++c) {
             const int ci = lane + 64 * c;
-            if (ci < nchunk) {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) { float d = v[c][j] - mean; q += d * d; }
-            }
-        }
-        const float rstd = rsqrtf(wave_sum(q) / (float)dim + eps);
-#pragma unroll
-        for (int c = 0; c < MAXC; ++c) {
-            const int ci = lane + 64 * c;
-            if (ci < nchunk) {
-                const int col = ci * 8;
-                const f32x4 sc0 = *reinterpret_cast<const f32x4*>(scale1p + col), sc1 = *reinterpret_cast<const f32x4*>(scale1p + col + 4);
-                const f32x4 sh0 = *reinterpret_cast<const f32x4*>(shift + col), sh1 = *reinterpret_cast<const f32x4*>(shift + col + 4);
-                bf16x8 o;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    float y = rbf((v[c][j] - mean) * rstd);
-                    y = rbf(rbf(y * (j < 4 ? sc0[j & 3] : sc1[j & 3])) + (j < 4 ? sh0[j & 3] : sh1[j & 3]));
-                    o[j] = (bf16)y;
-                }
-                st_bf16x8(out + roff + col, o);
-            }
+            if (ci < nchunk) st_bf16x8(p.out[br] + roff + ci * 8, ln_emit_chunk(v[c], mean, rstd, false, true, ln_load_vecs(false, true, nullptr, nullptr, shift, scale1p, ci * 8)));
         }
     }
 }
 
-// x, add_condition (may be null), res[k], out[k]: dense [rows, dim] bf16, 16-byte aligned.  Branch k (0 cond, 1 uncond, 2 drop-text) is served when
-// res[k] is given; with_addc[k] says whether its input is bf16(x + add_condition) (ignored without add_condition).  Only the out[k] are written.
+// p.addc[k] may be set only where add_condition is given; at least one branch is served
+static svi_status launch_add_ln_mod_skip(const bf16* x, const bf16* add_condition, const SviSkipRows& p, int nbr, int rows, int dim, float eps,
+                                         const float* shift, const float* scale1p, hipStream_t st) {
+    dim3 grid((rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK), block(256);
+    with_maxc(dim / 8, [&](auto mc) {
+        constexpr int MAXC = decltype(mc)::value;
+        if (nbr == 2) hipLaunchKernelGGL((add_ln_mod_skip_kernel<MAXC, 2, false>), grid, block, 0, st, x, add_condition, p, rows, dim, eps, shift, scale1p);
+        else if (add_condition) hipLaunchKernelGGL((add_ln_mod_skip_kernel<MAXC, 3, true>), grid, block, 0, st, x, add_condition, p, rows, dim, eps, shift, scale1p);
+        else hipLaunchKernelGGL((add_ln_mod_skip_kernel<MAXC, 3, false>), grid, block, 0, st, x, add_condition, p, rows, dim, eps, shift, scale1p);
+    });
+    SVI_LAUNCH_CHECK();
+    return SVI_OK;
+}
+
+// The CFG pair.  x, res_*, out_*: dense [rows, dim] bf16, 16-byte aligned; out_a / out_b are written, x and the residuals only read.
+// res_b / out_b may be null: one branch only.
+svi_status svi_launch_add_ln_mod_pair(const bf16* x, const bf16* res_a, const bf16* res_b, bf16* out_a, bf16* out_b, int rows, int dim, float eps,
+                                      const float* shift, const float* scale1p, hipStream_t st) {
+    SVI_REQUIRE(x && res_a && out_a && shift && scale1p && (res_b == nullptr) == (out_b == nullptr), "add + layernorm: null operand");
+    SVI_REQUIRE(dim % 8 == 0 && dim <= 8192, "add + layernorm: dim %d must be a multiple of 8, at most 8192", dim);
+    SVI_REQUIRE((((uintptr_t)x | (uintptr_t)res_a | (uintptr_t)res_b | (uintptr_t)out_a | (uintptr_t)out_b | (uintptr_t)shift | (uintptr_t)scale1p) & 15) == 0,
+                "add + layernorm: operands must be 16-byte aligned");
+    if (rows <= 0) return SVI_OK;
+    const SviSkipRows p{{res_a, res_b, nullptr}, {out_a, out_b, nullptr}, {0, 0, 0}};
+    return launch_add_ln_mod_skip(x, nullptr, p, 2, rows, dim, eps, shift, scale1p, st);
+}
+
+// The talk variant.  x, add_condition (may be null), res[k], out[k]: dense [rows, dim] bf16, 16-byte aligned.  Branch k (0 cond, 1 uncond, 2 drop-text) is
+// served when res[k] is given; with_addc[k] says whether its input is bf16(x + add_condition) (ignored without add_condition).  Only the out[k] are written.
 svi_status svi_launch_add_ln_mod_talk3(const bf16* x, const bf16* add_condition, const bf16* const res[3], bf16* const out[3], const bool with_addc[3],
                                        int rows, int dim, float eps, const float* shift, const float* scale1p, hipStream_t st) {
     SVI_REQUIRE(x && shift && scale1p, "add + layernorm (talk): null operand");
     SVI_REQUIRE(dim % 8 == 0 && dim <= 8192, "add + layernorm (talk): dim %d must be a multiple of 8, at most 8192", dim);
-    SviTalk3Skip p{};
+    SviSkipRows p{};
     uintptr_t bits = (uintptr_t)x | (uintptr_t)add_condition | (uintptr_t)shift | (uintptr_t)scale1p;
     bool any = false, any_addc = false;
     for (int k = 0; k < 3; ++k) {
@@ -773,17 +699,7 @@ svi_status svi_launch_add_ln_mod_talk3(const bf16* x, const bf16* add_condition,
     }
     SVI_REQUIRE((bits & 15) == 0, "add + layernorm (talk): operands must be 16-byte aligned");
     if (rows <= 0 || !any) return SVI_OK;
-    const bf16* ac = any_addc ? add_condition : nullptr;          // not read when no served branch has it
-    dim3 grid((rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK), block(256);
-    const int nchunk = dim / 8;
-    if (nchunk <= 64 * 3)
-        hipLaunchKernelGGL(add_ln_mod_talk3_kernel<3>, grid, block, 0, st, x, ac, p, rows, dim, eps, shift, scale1p);
-    else if (nchunk <= 64 * 10)
-        hipLaunchKernelGGL(add_ln_mod_talk3_kernel<10>, grid, block, 0, st, x, ac, p, rows, dim, eps, shift, scale1p);
-    else
-        hipLaunchKernelGGL(add_ln_mod_talk3_kernel<16>, grid, block, 0, st, x, ac, p, rows, dim, eps, shift, scale1p);
-    SVI_LAUNCH_CHECK();
-    return SVI_OK;
+    return launch_add_ln_mod_skip(x, any_addc ? add_condition : nullptr, p, 3, rows, dim, eps, shift, scale1p, st);          // not read when no served branch has it
 }
 
 
@@ -933,9 +849,7 @@ __global__ __launch_bounds__(256) void cfg3_step_kernel(bf16* __restrict__ lat, 
 svi_status svi_launch_cfg3_step(bf16* lat, const bf16* cond, const bf16* uncond, const bf16* drop, int64_t n, float st, float sa, float dsigma,
                                 hipStream_t stream) {
     if (n <= 0) return SVI_OK;
-    int blocks = (int)((n + 255) / 256);
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(cfg3_step_kernel, dim3(blocks), dim3(256), 0, stream, lat, cond, uncond, drop, n, st, sa, dsigma);
+    hipLaunchKernelGGL(cfg3_step_kernel, grid_1d(n, 2048), dim3(256), 0, stream, lat, cond, uncond, drop, n, st, sa, dsigma);
     SVI_LAUNCH_CHECK();
     return SVI_OK;
 }

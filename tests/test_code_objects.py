@@ -55,7 +55,7 @@ def test_hot_kernels_run_without_scratch_and_fit_their_occupancy(tmp_path):
         return got
     clean = {}
     for prefix in ("flash_cross_resident_kernel<", "gemm_bf16_nt_256e_kernel<", "gemm_bf16_nt_kernel", "gemm_mx8_nt_256_kernel", "ln_mod_rows_kernel<", "rmsnorm_rope_rows_kernel<",
-                   "row_rs_kernel", "cfg_step_kernel", "conv_dma2h_kernel<", "conv_dma2h_pair_kernel", "flash_fwd_kernel<"):
+                   "ln_mod_kernel<", "rmsnorm_rope_kernel<", "add_ln_mod_skip_kernel<", "row_rs_kernel", "cfg_step_kernel", "conv_dma2h_kernel<", "conv_dma2h_pair_kernel", "flash_fwd_kernel<"):
         clean.update(family(prefix))
     main_pass = {k: v for k, v in family("flash_fwd2_kernel<").items() if re.match(r"flash_fwd2_kernel<\d+, (true|false), 1, ", k)}
     assert len(main_pass) == 6, sorted(main_pass)

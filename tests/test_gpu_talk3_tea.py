@@ -29,12 +29,12 @@ TEA_STEPS, TEA_THRESH_MIXED, TEA_THRESH_FOUR = 8, 1.4e5, 2.0e5
 _MODELS = {}
 
 
-def _model(key="a"):
+def _model(key="a", cfg=CFG):
     import svi_hip
     m = _MODELS.get(key)
     if m is None:
-        sd = {k: torch.from_numpy(v) for k, v in synth.dit_state_dict(SEED, **CFG).items()}
-        m = _MODELS[key] = svi_hip.WanDiT.from_state_dict(sd, eps=1e-6, num_heads=synth.num_heads_of(CFG), **CFG)
+        sd = {k: torch.from_numpy(v) for k, v in synth.dit_state_dict(SEED, **cfg).items()}
+        m = _MODELS[key] = svi_hip.WanDiT.from_state_dict(sd, eps=1e-6, num_heads=synth.num_heads_of(cfg), **cfg)
     m.context_cache(False)
     m.set_audio(None)
     m.stage_audio(0, None)
@@ -42,7 +42,7 @@ def _model(key="a"):
     return m
 
 
-def _clip(grid, k=0, addc=True):
+def _clip(grid, k=0, addc=True, dim=CFG["dim"]):
     f, h, w = grid
     s = SEED + 100 * k
     x = dev(synth.randn(s + 1, 1, 16, f, 2 * h, 2 * w))
@@ -51,7 +51,7 @@ def _clip(grid, k=0, addc=True):
     kw = dict(clip_feature=dev(synth.randn(s + 3, 1, 257, 1280)), y=dev(synth.randn(s + 4, 1, 20, f, 2 * h, 2 * w)))
     aud = tuple(dev(a) for a in synth.audio_windows(s + 5, f))
     null = tuple(dev(a) for a in synth.audio_windows(s + 7, f))
-    add = dev(0.5 * synth.randn(s + 9, 1, f * h * w, CFG["dim"])) if addc else None
+    add = dev(0.5 * synth.randn(s + 9, 1, f * h * w, dim)) if addc else None
     return x, pos, neg, kw, aud, null, add
 
 
@@ -150,6 +150,44 @@ def test_talk3_tea_is_three_tea_forwards(grid, cache, addc):
     m.forward(x, TS_OLD, neg, tea_mode=1, residual=Nur, **kw)
     m.set_audio(None)
     assert torch.equal(Pg, P_old) and torch.equal(Nd, N_old) and torch.equal(Nu, Nur) and not torch.equal(Nu, Nd)
+
+
+# The skip kernel at a product width: the tiny talk model (dim 256) runs it with partly filled lanes only.  Dim 1536 is every lane full at three chunks; the
+# three armed forwards it is held against run add_bf16 (+ add_bf16) + svi_launch_ln_mod, the multi-row kernel at this width.  15 rows: the last workgroup
+# runs three.  The triples: every branch skips (three served rows, uncond without add_condition), cond and drop-text only, uncond and drop-text only.
+WIDE_CFG = dict(CFG, dim=1536, ffn_dim=256, num_layers=1)
+
+
+@pytest.mark.parametrize("addc", [False, True], ids=["plain", "addc"])
+def test_talk3_tea_skip_at_a_product_width(addc):
+    grid = (1, 3, 5)
+    m = _model("wide", WIDE_CFG)
+    m.context_cache(True)
+    clip = _clip(grid, addc=addc, dim=WIDE_CFG["dim"])
+    x, pos, neg, kw, aud, null, add = clip
+    L, D = grid[0] * grid[1] * grid[2], WIDE_CFG["dim"]
+    P_old, N_old = (torch.full((1, L, D), SENTINEL, dtype=torch.bfloat16, device="cuda") for _ in range(2))
+    _three_tea_forwards(m, clip, (1, 1, 1), P_old, N_old, ts=TS_OLD)
+    assert not (P_old == SENTINEL).all() and not (N_old == SENTINEL).all() and not torch.equal(P_old, N_old)
+    m.stage_audio(0, aud)
+    m.stage_audio(1, null)
+    plain = tuple(o.clone() for o in m.forward_talk3(x, TS, pos, neg, add_condition=add, **kw))
+    for modes in ((2, 2, 2), (2, 0, 2), (1, 2, 2)):
+        Pr, Nr, Pg, Ng = P_old.clone(), N_old.clone(), P_old.clone(), N_old.clone()
+        _prefill(modes, Pr, Nr)
+        _prefill(modes, Pg, Ng)
+        want = _three_tea_forwards(m, clip, modes, Pr, Nr)
+        got = tuple(o.clone() for o in m.forward_talk3(x, TS, pos, neg, add_condition=add, tea_modes=modes, residual_cond=Pg, residual_uncond=Ng,
+                                                       residual_drop_text=Ng, **kw))
+        for name, g, w in zip(("cond", "uncond", "drop_text"), got, want):
+            assert torch.equal(g, w), (modes, name, errs(g, w))
+        assert torch.equal(Pg, Pr) and torch.equal(Ng, Nr), (modes, "residuals")
+        assert torch.equal(Ng, N_old) and (torch.equal(Pg, P_old) == (modes[0] == 2))          # a skip reads its residual, a store replaces it
+        if modes == (2, 2, 2):
+            assert torch.equal(got[1], got[2]) == (not addc) and not torch.equal(got[0], got[1])
+        for k in range(3):
+            assert torch.equal(got[k], plain[k]) == (modes[k] != 2), (modes, k)                # a skipped branch is not a computed one
+    m.context_cache(False)
 
 
 def test_talk3_tea_refusals_leave_the_outputs_alone():

@@ -104,6 +104,52 @@ def test_pair_tea_is_bit_identical_to_two_tea_forwards(model, B, grid, cache, ad
     assert not torch.equal(a2, m.forward(x2, t2, cp, **kw))
 
 
+# The skip kernel at the product widths: the tiny models above run it at MAXC = 3 with partly filled lanes only.  Dim 1536 (1.3B) is MAXC = 3 and dim 5120
+# (14B) MAXC = 10, every lane full; the two forward(tea_mode=2) calls it is held against run add_bf16 + svi_launch_ln_mod, the multi-row kernel at these
+# widths.  (1, 3, 5): L = 15, no multiple of 8 (branch by branch) nor of the 4 rows per workgroup (the last one runs 3); (1, 4, 6) with the context cache:
+# L = 24, the stacked form (one launch serves both branches).  One block and narrow ffn / text widths: the models are built once per module.
+_WIDE = {}
+
+
+def wide_model(dim):
+    c = dict(dim=dim, in_dim=16, ffn_dim=256, out_dim=16, text_dim=64, freq_dim=256, patch_size=(1, 2, 2), num_layers=1, has_image_input=False)
+    if dim not in _WIDE:
+        _WIDE[dim] = build(c, 300 + dim)
+    return c, _WIDE[dim]
+
+
+@pytest.mark.parametrize("dim", [1536, 5120])
+@pytest.mark.parametrize("grid,cache", [((1, 3, 5), False), ((1, 4, 6), True)])
+def test_pair_tea_skip_at_the_product_widths(dim, grid, cache):
+    c, m = wide_model(dim)
+    seed = 300 + dim
+    x1, cp, cn, kw = clip_inputs(c, seed, grid)
+    x2 = dev(synth.randn(seed + 7, *x1.shape))
+    t1, t2 = torch.tensor([637.5]), torch.tensor([601.25])
+    L = grid[0] * grid[1] * grid[2]
+    ra, rb = (torch.full((1, L, dim), 7.0, dtype=torch.bfloat16, device="cuda") for _ in range(2))
+    m.context_cache(cache)
+    try:
+        a1 = m.forward(x1, t1, cp, tea_mode=1, residual=ra, **kw).clone()
+        b1 = m.forward(x1, t1, cn, tea_mode=1, residual=rb, **kw).clone()
+        a2 = m.forward(x2, t2, cp, tea_mode=2, residual=ra, **kw).clone()
+        b2 = m.forward(x2, t2, cn, tea_mode=2, residual=rb, **kw).clone()
+        A, Bn = Arena(1, L, dim), Arena(1, L, dim)
+        pa1, pb1 = (o.clone() for o in m.forward_cfg_pair(x1, t1, cp, cn, tea_mode=1, residual_cond=A.res, residual_uncond=Bn.res, **kw))
+        assert torch.equal(A.res, ra) and torch.equal(Bn.res, rb)
+        pa2, pb2 = m.forward_cfg_pair(x2, t2, cp, cn, tea_mode=2, residual_cond=A.res, residual_uncond=Bn.res, **kw)
+        computed = m.forward(x2, t2, cp, **kw)
+    finally:
+        m.context_cache(False)
+    assert torch.equal(pa1, a1) and torch.equal(pb1, b1)
+    assert torch.equal(pa2, a2) and torch.equal(pb2, b2)
+    assert torch.equal(A.res, ra) and torch.equal(Bn.res, rb)       # the skip reads the residuals, it does not write them
+    assert A.guards_intact() and Bn.guards_intact()
+    # not vacuous: the branches differ, the residuals differ, a skipped step is not a computed one
+    assert not torch.equal(ra, rb) and not torch.equal(a1, b1) and not torch.equal(a2, b2) and torch.isfinite(a2.float()).all()
+    assert not torch.equal(a2, computed)
+
+
 # ---- 2. refusals -----------------------------------------------------------------------------------------------------------------
 def test_pair_tea_refusals():
     from svi_hip import _lib as L

@@ -1717,7 +1717,7 @@ struct svi_vae {
     std::map<std::string, float> gamma_bound;           // key = full name: sqrt(C) * max|gamma| (0: unusable, see svi_vae_bind_weight)
     // workspace
     char* pool = nullptr;
-    size_t pool_bytes = 0, slot_bytes = 0;
+    size_t slot_bytes = 0;
     int nslots = 0;
     std::vector<int> slot_used;
     float* consts = nullptr;                            // mean[16] | inv_std[16]
@@ -1727,7 +1727,6 @@ struct svi_vae {
     bool pack_pending = false;                          // weight packing kernels enqueued on the null stream since the last call
     float* blend_w = nullptr; size_t blend_bytes = 0;   // mask accumulator of the tiled paths ([H, W] plane)
     const TileWin* win = nullptr;                       // set while a tile of svi_vae_tiled_* runs through the graphs
-    float* blend_values = nullptr;
 };
 
 namespace {
@@ -1818,6 +1817,15 @@ void free_t(svi_vae* h, Tens& t) {
     t.p = nullptr;
 }
 #define NEED(t) do { if (!h->dry && !(t).p) { svi_set_error("VAE tensor pool exhausted"); return SVI_ERR_OOM; } } while (0)
+
+// Grid of a one-dimensional kernel of 256-thread workgroups that gives each of its n elements one thread (no grid stride): refused
+// where one launch cannot hold them.  `what` names the tensor in the message.
+static svi_status grid_256(long n, const char* what, dim3* grid) {
+    const long groups = (n + 255) / 256;
+    SVI_REQUIRE(n >= 0 && groups < (1L << 31), "%s is too large for one launch (%ld elements)", what, n);
+    *grid = dim3((unsigned)groups);
+    return SVI_OK;
+}
 
 static float scale_of_bound(float bound) {          // largest power of two s with bound * s <= 2^15 (0: no usable bound)
     if (!(bound > 0.f && bound < 1e30f)) return 0.f;
@@ -1969,19 +1977,26 @@ svi_status attn_block(svi_vae* h, const std::string& p, Tens* x, hipStream_t st)
     return SVI_OK;
 }
 
+// What the time_conv of both Resample blocks shares (3 taps in time, 1x1 in space, x -> out at out's channel pitch); the caller sets
+// To, st, pt and how output frames are placed.
+static ConvP time_conv_params(const ConvW& c, const Tens& x, const Tens& out) {
+    ConvP q{};
+    q.in = x.p; q.Ti = x.T; q.Hi = x.H; q.Wi = x.W; q.Cin = c.Cin; q.ld_in = x.C;
+    q.w = c.packed; q.ld_w = c.ldw; q.bias = c.b_user;
+    q.w3 = c.packed3; q.ld_w3 = c.ldw3; q.plane_w3 = (long)c.kt * c.kh * c.kw * c.Cout * c.ldw3;
+    q.out = out.p; q.Ho = x.H; q.Wo = x.W; q.Cout = c.Cout; q.ld_out = out.C;
+    q.kt = 3; q.kh = q.kw = 1; q.sh = q.sw = 1;
+    return q;
+}
+
 // Resample 'upsample2d' / 'upsample3d' (vae:120-160)
 svi_status upsample_block(svi_vae* h, const std::string& p, Tens* x, bool temporal, hipStream_t st) {
     if (temporal && x->T > 1) {
-        const ConvW& c = h->convs.at(p + "time_conv");
         Tens up = alloc_t(h, 1 + 2 * (x->T - 1), x->H, x->W, x->C);
         NEED(up);
         if (!h->dry) {
-            ConvP q{};
-            q.in = x->p; q.Ti = x->T; q.Hi = x->H; q.Wi = x->W; q.Cin = c.Cin; q.ld_in = x->C;
-            q.w = c.packed; q.ld_w = c.ldw; q.bias = c.b_user;
-            q.w3 = c.packed3; q.ld_w3 = c.ldw3; q.plane_w3 = (long)c.kt * c.kh * c.kw * c.Cout * c.ldw3;
-            q.out = up.p; q.To = x->T; q.Ho = x->H; q.Wo = x->W; q.Cout = c.Cout; q.ld_out = up.C;
-            q.kt = 3; q.kh = q.kw = 1; q.st = q.sh = q.sw = 1; q.pt = 2;
+            ConvP q = time_conv_params(h->convs.at(p + "time_conv"), *x, up);
+            q.To = x->T; q.st = 1; q.pt = 2;
             q.zero_frame0 = 1; q.t_begin = 1; q.out_mode = 1;
             { SviProfScope _p(PROF_VAE_CONV, st); SVI_TRY(launch_conv(q, st)); }
             SVI_CHECK_HIP(hipMemcpyAsync(up.p, x->p, (size_t)x->H * x->W * x->C * 4, hipMemcpyDeviceToDevice, st));
@@ -2003,17 +2018,12 @@ svi_status downsample_block(svi_vae* h, const std::string& p, Tens* x, bool temp
     free_t(h, *x);
     *x = sp;
     if (temporal && x->T > 1) {
-        const ConvW& c = h->convs.at(p + "time_conv");
         const int To = (x->T - 3) / 2 + 1;
         Tens dn = alloc_t(h, 1 + To, x->H, x->W, x->C);
         NEED(dn);
         if (!h->dry) {
-            ConvP q{};
-            q.in = x->p; q.Ti = x->T; q.Hi = x->H; q.Wi = x->W; q.Cin = c.Cin; q.ld_in = x->C;
-            q.w = c.packed; q.ld_w = c.ldw; q.bias = c.b_user;
-            q.w3 = c.packed3; q.ld_w3 = c.ldw3; q.plane_w3 = (long)c.kt * c.kh * c.kw * c.Cout * c.ldw3;
-            q.out = dn.p; q.To = To; q.Ho = x->H; q.Wo = x->W; q.Cout = c.Cout; q.ld_out = dn.C;
-            q.kt = 3; q.kh = q.kw = 1; q.st = 2; q.sh = q.sw = 1; q.pt = 0;
+            ConvP q = time_conv_params(h->convs.at(p + "time_conv"), *x, dn);
+            q.To = To; q.st = 2; q.pt = 0;
             q.t_out_off = 1;
             { SviProfScope _p(PROF_VAE_CONV, st); SVI_TRY(launch_conv(q, st)); }
             SVI_CHECK_HIP(hipMemcpyAsync(dn.p, x->p, (size_t)x->H * x->W * x->C * 4, hipMemcpyDeviceToDevice, st));
@@ -2021,46 +2031,6 @@ svi_status downsample_block(svi_vae* h, const std::string& p, Tens* x, bool temp
         free_t(h, *x);
         *x = dn;
     }
-    return SVI_OK;
-}
-
-svi_status decode_graph(svi_vae* h, const float* latents, float* video, int T, int hh, int ww, hipStream_t st) {
-    const std::string d = "model.decoder.";
-    Tens z = alloc_t(h, T, hh, ww, 16);
-    NEED(z);
-    if (!h->dry) {
-        const long n = (long)T * hh * ww * 16;
-        if (h->win) hipLaunchKernelGGL(latent_in_win_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, latents, z.p, T, *h->win, h->consts, h->consts + 16);
-        else hipLaunchKernelGGL(latent_in_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, latents, z.p, (long)T * hh * ww, h->consts, h->consts + 16);
-        SVI_LAUNCH_CHECK();
-    }
-    Tens x, t2;
-    SVI_TRY(conv_layer(h, "model.conv2", z, &t2, st));
-    free_t(h, z);
-    SVI_TRY(conv_layer(h, d + "conv1", t2, &x, st));
-    free_t(h, t2);
-    SVI_TRY(res_block(h, d + "middle.0.", &x, st));
-    SVI_TRY(attn_block(h, d + "middle.1.", &x, st));
-    SVI_TRY(res_block(h, d + "middle.2.", &x, st));
-    const bool tup[3] = {true, true, false};
-    int idx = 0;
-    for (int i = 0; i < 4; ++i) {
-        for (int r = 0; r < 3; ++r) SVI_TRY(res_block(h, d + "upsamples." + std::to_string(idx++) + ".", &x, st));
-        if (i != 3) SVI_TRY(upsample_block(h, d + "upsamples." + std::to_string(idx++) + ".", &x, tup[i], st));
-    }
-    Tens n, rgb;
-    SVI_TRY(norm_act(h, d + "head.0.gamma", x, &n, 1, st, planes_scale_for(h, d + "head.2", d + "head.0.gamma", x)));
-    free_t(h, x);
-    SVI_TRY(conv_layer(h, d + "head.2", n, &rgb, st));
-    free_t(h, n);
-    if (!h->dry) {
-        const long thw = (long)rgb.T * rgb.H * rgb.W;
-        if (h->win) hipLaunchKernelGGL(tile_blend_kernel, dim3((unsigned)((thw + 255) / 256)), dim3(256), 0, st, rgb.p, rgb.C, video, h->blend_w, 3, rgb.T,
-                                       rgb.H, rgb.W, *h->win, 0, h->consts, h->consts + 16);
-        else hipLaunchKernelGGL(video_out_kernel, dim3((unsigned)((thw * 3 + 255) / 256)), dim3(256), 0, st, rgb.p, rgb.C, video, thw);
-        SVI_LAUNCH_CHECK();
-    }
-    free_t(h, rgb);
     return SVI_OK;
 }
 
@@ -2074,6 +2044,13 @@ struct SplitPlan {
     int halo[4];                     // per side, in pixels of the stage's resolution (latent x 2^s)
     int pad[4][4];                   // rectangle entering stage s, in that stage's resolution: owned x 2^s grown by halo[s], clamped to the image
 };
+
+// The flat int32 plans of the C ABI ARE the plan structs as they lie in memory (SplitPlan: 24 values, EncSplitPlan: 34), fields in
+// declaration order, arrays row-major: the struct is the one description of the layout, the asserts beside each hold it in place.
+template <class Plan> static void plan_to_flat(const Plan& pl, int32_t* flat) { memcpy(flat, &pl, sizeof(Plan)); }
+template <class Plan> static Plan plan_from_flat(const int32_t* flat) { Plan pl; memcpy(&pl, flat, sizeof(Plan)); return pl; }
+static_assert(sizeof(int) == sizeof(int32_t) && sizeof(SplitPlan) == 24 * sizeof(int32_t) && offsetof(SplitPlan, halo) == 4 * sizeof(int32_t) &&
+              offsetof(SplitPlan, pad) == 8 * sizeof(int32_t), "svi_vae_split_plan's out24 is SplitPlan in memory");
 
 // The decoder behind the middle block, as decode_graph walks it: three residual blocks per stage, an upsample block behind stages 0-2.
 struct DecStage { std::string res[3], up; bool temporal; };
@@ -2112,14 +2089,21 @@ static void decoder_halos(int halo[4]) {
     }
 }
 
-static svi_status split_plan(int hh, int ww, int parts_h, int parts_w, int part, SplitPlan* pl) {
-    SVI_REQUIRE(hh > 0 && ww > 0 && parts_h > 0 && parts_w > 0, "svi_vae_split_plan: the grid and the split must be positive (got %d x %d in %d x %d parts)", hh, ww, parts_h, parts_w);
-    SVI_REQUIRE(hh <= (1 << 20) && ww <= (1 << 20), "svi_vae_split_plan: latent grid %d x %d is too large", hh, ww);
-    SVI_REQUIRE(parts_h <= hh && parts_w <= ww, "svi_vae_split_plan: %d x %d parts of a %d x %d latent grid would leave a part without a pixel", parts_h, parts_w, hh, ww);
-    SVI_REQUIRE(part >= 0 && part < parts_h * parts_w, "svi_vae_split_plan: part %d is outside the %d x %d split", part, parts_h, parts_w);
+// The split grid of both directions: part `part` (row-major) of parts_h x parts_w owns the latent rectangle own = {h0, h1, w0, w1}, cut at
+// floor(i * hh / parts_h), floor(j * ww / parts_w).  `api` names the caller's entry point in the messages.
+static svi_status split_own(const char* api, int hh, int ww, int parts_h, int parts_w, int part, int own[4]) {
+    SVI_REQUIRE(hh > 0 && ww > 0 && parts_h > 0 && parts_w > 0, "%s: the grid and the split must be positive (got %d x %d in %d x %d parts)", api, hh, ww, parts_h, parts_w);
+    SVI_REQUIRE(hh <= (1 << 20) && ww <= (1 << 20), "%s: latent grid %d x %d is too large", api, hh, ww);
+    SVI_REQUIRE(parts_h <= hh && parts_w <= ww, "%s: %d x %d parts of a %d x %d latent grid would leave a part without a pixel", api, parts_h, parts_w, hh, ww);
+    SVI_REQUIRE(part >= 0 && part < parts_h * parts_w, "%s: part %d is outside the %d x %d split", api, part, parts_h, parts_w);
     const int i = part / parts_w, j = part % parts_w;
-    pl->own[0] = (int)((long)i * hh / parts_h); pl->own[1] = (int)((long)(i + 1) * hh / parts_h);
-    pl->own[2] = (int)((long)j * ww / parts_w); pl->own[3] = (int)((long)(j + 1) * ww / parts_w);
+    own[0] = (int)((long)i * hh / parts_h); own[1] = (int)((long)(i + 1) * hh / parts_h);
+    own[2] = (int)((long)j * ww / parts_w); own[3] = (int)((long)(j + 1) * ww / parts_w);
+    return SVI_OK;
+}
+
+static svi_status split_plan(int hh, int ww, int parts_h, int parts_w, int part, SplitPlan* pl) {
+    SVI_TRY(split_own("svi_vae_split_plan", hh, ww, parts_h, parts_w, part, pl->own));
     decoder_halos(pl->halo);
     for (int s = 0; s < 4; ++s) {
         const int hal_h = parts_h > 1 ? pl->halo[s] : 0, hal_w = parts_w > 1 ? pl->halo[s] : 0;
@@ -2185,9 +2169,10 @@ svi_status crop_t(svi_vae* h, Tens* x, int y0, int x0, int hc, int wc, hipStream
     out.bound = x->bound;
     if (!h->dry) {
         const long n = out.elems() / 4;
-        SVI_REQUIRE((n + 255) / 256 < (1L << 31), "VAE crop: %ld elements need more workgroups than one launch has", out.elems());
+        dim3 grid;
+        SVI_TRY(grid_256(n, "VAE crop: the window", &grid));
         SviProfScope _p(PROF_VAE_OTHER, st);
-        hipLaunchKernelGGL(crop_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, reinterpret_cast<const float4*>(x->p), reinterpret_cast<float4*>(out.p), n,
+        hipLaunchKernelGGL(crop_kernel, grid, dim3(256), 0, st, reinterpret_cast<const float4*>(x->p), reinterpret_cast<float4*>(out.p), n,
                            x->H, x->W, x->C / 4, y0, x0, hc, wc);
         SVI_LAUNCH_CHECK();
     }
@@ -2196,14 +2181,21 @@ svi_status crop_t(svi_vae* h, Tens* x, int y0, int x0, int hc, int wc, hipStream
     return SVI_OK;
 }
 
-svi_status decode_part_graph(svi_vae* h, const float* latents, float* video, int T, int hh, int ww, const SplitPlan& pl, long ld_h, long ld_w, hipStream_t st) {
+// The one walk of the decoder.  The layers are the same on every path; the two ends differ:
+//   whole decode (pl null, no tile):  latent_in_kernel      ... video_out_kernel
+//   a tile (h->win set, pl null):     latent_in_win_kernel  ... tile_blend_kernel into `video` and h->blend_w
+//   a part (pl):                      latent_in_kernel      ... video_out_part_kernel at the pitches ld_h x ld_w, the activation cropped to
+//                                     the plan's rectangle behind the middle block and behind every upsample block
+// (hh, ww) is the latent that runs through the layers: the whole one, or a tile's window.  ld_h / ld_w are read with a plan only.
+svi_status decode_graph(svi_vae* h, const float* latents, float* video, int T, int hh, int ww, const SplitPlan* pl, long ld_h, long ld_w, hipStream_t st) {
     const std::string d = "model.decoder.";
     Tens z = alloc_t(h, T, hh, ww, 16);
     NEED(z);
     if (!h->dry) {
-        const long n = (long)T * hh * ww * 16;
-        SVI_REQUIRE((n + 255) / 256 < (1L << 31), "svi_vae_decode_part: the latent is too large for one launch");
-        hipLaunchKernelGGL(latent_in_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, latents, z.p, (long)T * hh * ww, h->consts, h->consts + 16);
+        dim3 grid;
+        SVI_TRY(grid_256((long)T * hh * ww * 16, "VAE decode: the latent", &grid));
+        if (h->win) hipLaunchKernelGGL(latent_in_win_kernel, grid, dim3(256), 0, st, latents, z.p, T, *h->win, h->consts, h->consts + 16);
+        else hipLaunchKernelGGL(latent_in_kernel, grid, dim3(256), 0, st, latents, z.p, (long)T * hh * ww, h->consts, h->consts + 16);
         SVI_LAUNCH_CHECK();
     }
     Tens x, t2;
@@ -2216,14 +2208,16 @@ svi_status decode_part_graph(svi_vae* h, const float* latents, float* video, int
     SVI_TRY(res_block(h, d + "middle.2.", &x, st));
     DecStage stg[4];
     decoder_stages(stg);
-    SVI_TRY(crop_t(h, &x, pl.pad[0][0], pl.pad[0][2], pl.pad[0][1] - pl.pad[0][0], pl.pad[0][3] - pl.pad[0][2], st));
+    if (pl) SVI_TRY(crop_t(h, &x, pl->pad[0][0], pl->pad[0][2], pl->pad[0][1] - pl->pad[0][0], pl->pad[0][3] - pl->pad[0][2], st));
     for (int i = 0; i < 4; ++i) {
         for (int r = 0; r < 3; ++r) SVI_TRY(res_block(h, stg[i].res[r], &x, st));
         if (i != 3) {
             SVI_TRY(upsample_block(h, stg[i].up, &x, stg[i].temporal, st));
-            const int* q = pl.pad[i];            // x now covers 2 q; trim it to what the stages behind still need
-            const int* r = pl.pad[i + 1];
-            SVI_TRY(crop_t(h, &x, r[0] - 2 * q[0], r[2] - 2 * q[2], r[1] - r[0], r[3] - r[2], st));
+            if (pl) {
+                const int* q = pl->pad[i];           // x now covers 2 q; trim it to what the stages behind still need
+                const int* r = pl->pad[i + 1];
+                SVI_TRY(crop_t(h, &x, r[0] - 2 * q[0], r[2] - 2 * q[2], r[1] - r[0], r[3] - r[2], st));
+            }
         }
     }
     Tens n, rgb;
@@ -2232,11 +2226,21 @@ svi_status decode_part_graph(svi_vae* h, const float* latents, float* video, int
     SVI_TRY(conv_layer(h, d + "head.2", n, &rgb, st));
     free_t(h, n);
     if (!h->dry) {
-        const int y0 = 8 * pl.own[0] - pl.pad[3][0], x0 = 8 * pl.own[2] - pl.pad[3][2], oh = 8 * (pl.own[1] - pl.own[0]), ow = 8 * (pl.own[3] - pl.own[2]);
-        SVI_REQUIRE(y0 >= 0 && x0 >= 0 && y0 + oh <= rgb.H && x0 + ow <= rgb.W, "svi_vae_decode_part: the owned window leaves the decoded crop");
-        const long cnt = 3L * rgb.T * oh * ow;
-        SVI_REQUIRE((cnt + 255) / 256 < (1L << 31), "svi_vae_decode_part: the owned window is too large for one launch");
-        hipLaunchKernelGGL(video_out_part_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, rgb.p, rgb.C, video, cnt, rgb.T, rgb.H, rgb.W, y0, x0, oh, ow, ld_h, ld_w);
+        const long thw = (long)rgb.T * rgb.H * rgb.W;
+        dim3 grid;
+        if (h->win) {
+            SVI_TRY(grid_256(thw, "VAE tiled decode: the tile", &grid));
+            hipLaunchKernelGGL(tile_blend_kernel, grid, dim3(256), 0, st, rgb.p, rgb.C, video, h->blend_w, 3, rgb.T, rgb.H, rgb.W, *h->win, 0, h->consts, h->consts + 16);
+        } else if (pl) {
+            const int y0 = 8 * pl->own[0] - pl->pad[3][0], x0 = 8 * pl->own[2] - pl->pad[3][2], oh = 8 * (pl->own[1] - pl->own[0]), ow = 8 * (pl->own[3] - pl->own[2]);
+            SVI_REQUIRE(y0 >= 0 && x0 >= 0 && y0 + oh <= rgb.H && x0 + ow <= rgb.W, "svi_vae_decode_part: the owned window leaves the decoded crop");
+            const long cnt = 3L * rgb.T * oh * ow;
+            SVI_TRY(grid_256(cnt, "svi_vae_decode_part: the owned window", &grid));
+            hipLaunchKernelGGL(video_out_part_kernel, grid, dim3(256), 0, st, rgb.p, rgb.C, video, cnt, rgb.T, rgb.H, rgb.W, y0, x0, oh, ow, ld_h, ld_w);
+        } else {
+            SVI_TRY(grid_256(thw * 3, "VAE decode: the video", &grid));
+            hipLaunchKernelGGL(video_out_kernel, grid, dim3(256), 0, st, rgb.p, rgb.C, video, thw);
+        }
         SVI_LAUNCH_CHECK();
     }
     free_t(h, rgb);
@@ -2259,16 +2263,17 @@ svi_status encode_tail_layers(svi_vae* h, Tens* x, float* latents, hipStream_t s
     free_t(h, hd);
     if (!h->dry) {
         const long thw = (long)mu.T * mu.H * mu.W;
-        if (h->win) hipLaunchKernelGGL(tile_blend_kernel, dim3((unsigned)((thw + 255) / 256)), dim3(256), 0, st, mu.p, mu.C, latents, h->blend_w, 16, mu.T,
-                                       mu.H, mu.W, *h->win, 1, h->consts, h->consts + 16);
-        else hipLaunchKernelGGL(latent_out_kernel, dim3((unsigned)((thw * 16 + 255) / 256)), dim3(256), 0, st, mu.p, mu.C, latents, thw, h->consts, h->consts + 16);
+        dim3 grid;
+        SVI_TRY(grid_256(h->win ? thw : thw * 16, h->win ? "VAE tiled encode: the tile" : "VAE encode: the latent", &grid));
+        if (h->win) hipLaunchKernelGGL(tile_blend_kernel, grid, dim3(256), 0, st, mu.p, mu.C, latents, h->blend_w, 16, mu.T, mu.H, mu.W, *h->win, 1, h->consts, h->consts + 16);
+        else hipLaunchKernelGGL(latent_out_kernel, grid, dim3(256), 0, st, mu.p, mu.C, latents, thw, h->consts, h->consts + 16);
         SVI_LAUNCH_CHECK();
     }
     free_t(h, mu);
     return SVI_OK;
 }
 
-// The encoder in front of the middle block, as encode_graph walks it: two residual blocks per stage, a downsample block behind stages 0-2.
+// The encoder in front of the middle block, as encode_front walks it: two residual blocks per stage, a downsample block behind stages 0-2.
 struct EncStage { std::string res[2], down; bool temporal; };
 static void encoder_stages(EncStage out[4]) {
     const std::string e = "model.encoder.";
@@ -2279,28 +2284,6 @@ static void encoder_stages(EncStage out[4]) {
         out[i].down = i != 3 ? e + "downsamples." + std::to_string(idx++) + "." : std::string();
         out[i].temporal = i != 3 && tdown[i];
     }
-}
-
-svi_status encode_graph(svi_vae* h, const float* video, float* latents, int T, int H, int W, hipStream_t st) {
-    const std::string e = "model.encoder.";
-    Tens v = alloc_t(h, T, H, W, 4);
-    NEED(v);
-    if (!h->dry) {
-        const long thw = (long)T * H * W;
-        if (h->win) hipLaunchKernelGGL(video_in_win_kernel, dim3((unsigned)((thw * 4 + 255) / 256)), dim3(256), 0, st, video, v.p, T, *h->win);
-        else hipLaunchKernelGGL(video_in_kernel, dim3((unsigned)((thw * 4 + 255) / 256)), dim3(256), 0, st, video, v.p, thw);
-        SVI_LAUNCH_CHECK();
-    }
-    Tens x;
-    SVI_TRY(conv_layer(h, e + "conv1", v, &x, st));
-    free_t(h, v);
-    EncStage stg[4];
-    encoder_stages(stg);
-    for (int i = 0; i < 4; ++i) {
-        for (int r = 0; r < 2; ++r) SVI_TRY(res_block(h, stg[i].res[r], &x, st));
-        if (i != 3) SVI_TRY(downsample_block(h, stg[i].down, &x, stg[i].temporal, st));
-    }
-    return encode_tail_layers(h, &x, latents, st);
 }
 
 // ---- exact spatial split of the encode (svi_vae_encode_split_plan / svi_vae_encode_part / svi_vae_encode_tail) -----------------------
@@ -2314,6 +2297,8 @@ struct EncSplitPlan {
     int reach[5][2];                 // {top/left, bottom/right} at the entry points video, stage 0, 1, 2, 3, in pixels of that resolution
     int rect[5][4];                  // rectangle needed at those entry points, in that resolution (video and stage 0: x 8; stage s: x 2^(3-s))
 };
+static_assert(sizeof(EncSplitPlan) == 34 * sizeof(int32_t) && offsetof(EncSplitPlan, reach) == 4 * sizeof(int32_t) &&
+              offsetof(EncSplitPlan, rect) == 14 * sizeof(int32_t), "svi_vae_encode_split_plan's out34 is EncSplitPlan in memory");
 static inline int enc_factor(int entry) { return entry == 0 ? 8 : 8 >> (entry - 1); }      // resolution of an entry point relative to the latent grid
 
 // How far the layers between each entry point and the entry of middle.0 reach, from the architecture table, walked backwards: a residual
@@ -2346,13 +2331,7 @@ static void encoder_reaches(int reach[5][2]) {
 }
 
 static svi_status encode_split_plan(int hh, int ww, int parts_h, int parts_w, int part, EncSplitPlan* pl) {
-    SVI_REQUIRE(hh > 0 && ww > 0 && parts_h > 0 && parts_w > 0, "svi_vae_encode_split_plan: the grid and the split must be positive (got %d x %d in %d x %d parts)", hh, ww, parts_h, parts_w);
-    SVI_REQUIRE(hh <= (1 << 20) && ww <= (1 << 20), "svi_vae_encode_split_plan: latent grid %d x %d is too large", hh, ww);
-    SVI_REQUIRE(parts_h <= hh && parts_w <= ww, "svi_vae_encode_split_plan: %d x %d parts of a %d x %d latent grid would leave a part without a pixel", parts_h, parts_w, hh, ww);
-    SVI_REQUIRE(part >= 0 && part < parts_h * parts_w, "svi_vae_encode_split_plan: part %d is outside the %d x %d split", part, parts_h, parts_w);
-    const int i = part / parts_w, j = part % parts_w;
-    pl->own[0] = (int)((long)i * hh / parts_h); pl->own[1] = (int)((long)(i + 1) * hh / parts_h);
-    pl->own[2] = (int)((long)j * ww / parts_w); pl->own[3] = (int)((long)(j + 1) * ww / parts_w);
+    SVI_TRY(split_own("svi_vae_encode_split_plan", hh, ww, parts_h, parts_w, part, pl->own));
     encoder_reaches(pl->reach);
     for (int k = 0; k < 5; ++k) {
         // the origin keeps the phase of every stride-2 convolution behind it: a multiple of the entry point's factor, the need rounded up
@@ -2403,8 +2382,51 @@ __global__ __launch_bounds__(256) void feat_out_part_kernel(const float4* __rest
     out[((t * ld_h + y) * ld_w + x) * c4 + c] = in[((t * H + y0 + y) * W + x0 + x) * c4 + c];
 }
 
+// The encoder in front of the middle block: conv1 and the four down stages on the staged video v (consumed), leaving in *x the feature
+// map entering middle.0.  With a plan (a part) the activation is cropped to the plan's rectangle behind conv1 and behind every
+// downsample block; without one (the whole video, a tile) nothing is cropped.
+svi_status encode_front(svi_vae* h, Tens* v, Tens* x, const EncSplitPlan* pl, hipStream_t st) {
+    SVI_TRY(conv_layer(h, "model.encoder.conv1", *v, x, st));
+    free_t(h, *v);
+    if (pl) {
+        const int* vr = pl->rect[0];
+        const int* r = pl->rect[1];
+        SVI_TRY(crop_t(h, x, r[0] - vr[0], r[2] - vr[2], r[1] - r[0], r[3] - r[2], st));
+    }
+    EncStage stg[4];
+    encoder_stages(stg);
+    for (int i = 0; i < 4; ++i) {
+        for (int r = 0; r < 2; ++r) SVI_TRY(res_block(h, stg[i].res[r], x, st));
+        if (i != 3) {
+            SVI_TRY(downsample_block(h, stg[i].down, x, stg[i].temporal, st));
+            if (pl) {
+                const int* q = pl->rect[1 + i];          // x now covers [q0 / 2, q0 / 2 + (q1 - q0) / 2); trim it to what the stages behind still need
+                const int* r = pl->rect[2 + i];
+                SVI_TRY(crop_t(h, x, r[0] - q[0] / 2, r[2] - q[2] / 2, r[1] - r[0], r[3] - r[2], st));
+            }
+        }
+    }
+    return SVI_OK;
+}
+
+// The whole encode, or one tile of svi_vae_tiled_encode (h->win set: (H, W) is the tile's window, the tail blends it into `latents`).
+svi_status encode_graph(svi_vae* h, const float* video, float* latents, int T, int H, int W, hipStream_t st) {
+    Tens v = alloc_t(h, T, H, W, 4);
+    NEED(v);
+    if (!h->dry) {
+        const long thw = (long)T * H * W;
+        dim3 grid;
+        SVI_TRY(grid_256(thw * 4, "VAE encode: the video", &grid));
+        if (h->win) hipLaunchKernelGGL(video_in_win_kernel, grid, dim3(256), 0, st, video, v.p, T, *h->win);
+        else hipLaunchKernelGGL(video_in_kernel, grid, dim3(256), 0, st, video, v.p, thw);
+        SVI_LAUNCH_CHECK();
+    }
+    Tens x;
+    SVI_TRY(encode_front(h, &v, &x, nullptr, st));
+    return encode_tail_layers(h, &x, latents, st);
+}
+
 svi_status encode_part_graph(svi_vae* h, const float* video, float* feat_out, int T, int H, int W, const EncSplitPlan& pl, long ld_h, long ld_w, hipStream_t st) {
-    const std::string e = "model.encoder.";
     const int* vr = pl.rect[0];
     Tens v = alloc_t(h, T, vr[1] - vr[0], vr[3] - vr[2], 4);
     NEED(v);
@@ -2412,37 +2434,22 @@ svi_status encode_part_graph(svi_vae* h, const float* video, float* feat_out, in
         TileWin w{};
         w.Hf = H; w.Wf = W; w.h0 = vr[0]; w.w0 = vr[2]; w.th = v.H; w.tw = v.W;
         SVI_REQUIRE(w.h0 >= 0 && w.w0 >= 0 && w.h0 + w.th <= H && w.w0 + w.tw <= W, "svi_vae_encode_part: the video window leaves the %d x %d video", H, W);
-        const long n = v.elems();
-        SVI_REQUIRE((n + 255) / 256 < (1L << 31), "svi_vae_encode_part: the video window is too large for one launch");
-        hipLaunchKernelGGL(video_in_win_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, video, v.p, T, w);
+        dim3 grid;
+        SVI_TRY(grid_256(v.elems(), "svi_vae_encode_part: the video window", &grid));
+        hipLaunchKernelGGL(video_in_win_kernel, grid, dim3(256), 0, st, video, v.p, T, w);
         SVI_LAUNCH_CHECK();
     }
     Tens x;
-    SVI_TRY(conv_layer(h, e + "conv1", v, &x, st));
-    free_t(h, v);
-    {
-        const int* r = pl.rect[1];
-        SVI_TRY(crop_t(h, &x, r[0] - vr[0], r[2] - vr[2], r[1] - r[0], r[3] - r[2], st));
-    }
-    EncStage stg[4];
-    encoder_stages(stg);
-    for (int i = 0; i < 4; ++i) {
-        for (int r = 0; r < 2; ++r) SVI_TRY(res_block(h, stg[i].res[r], &x, st));
-        if (i != 3) {
-            SVI_TRY(downsample_block(h, stg[i].down, &x, stg[i].temporal, st));
-            const int* q = pl.rect[1 + i];           // x now covers [q0 / 2, q0 / 2 + (q1 - q0) / 2); trim it to what the stages behind still need
-            const int* r = pl.rect[2 + i];
-            SVI_TRY(crop_t(h, &x, r[0] - q[0] / 2, r[2] - q[2] / 2, r[1] - r[0], r[3] - r[2], st));
-        }
-    }
+    SVI_TRY(encode_front(h, &v, &x, &pl, st));
     if (!h->dry) {
         const int y0 = pl.own[0] - pl.rect[4][0], x0 = pl.own[2] - pl.rect[4][2], oh = pl.own[1] - pl.own[0], ow = pl.own[3] - pl.own[2];
         SVI_REQUIRE(y0 >= 0 && x0 >= 0 && y0 + oh <= x.H && x0 + ow <= x.W, "svi_vae_encode_part: the owned window leaves the encoded crop");
         SVI_REQUIRE(x.T == 1 + (T - 1) / 4 && x.C % 4 == 0 && x.plane_scale == 0.f, "svi_vae_encode_part: unexpected feature map [%d, %d, %d, %d]", x.T, x.H, x.W, x.C);
         const long n = (long)x.T * oh * ow * (x.C / 4);
-        SVI_REQUIRE((n + 255) / 256 < (1L << 31), "svi_vae_encode_part: the owned window is too large for one launch");
+        dim3 grid;
+        SVI_TRY(grid_256(n, "svi_vae_encode_part: the owned window", &grid));
         SviProfScope _p(PROF_VAE_OTHER, st);
-        hipLaunchKernelGGL(feat_out_part_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, reinterpret_cast<const float4*>(x.p), reinterpret_cast<float4*>(feat_out), n,
+        hipLaunchKernelGGL(feat_out_part_kernel, grid, dim3(256), 0, st, reinterpret_cast<const float4*>(x.p), reinterpret_cast<float4*>(feat_out), n,
                            x.H, x.W, x.C / 4, y0, x0, oh, ow, ld_h, ld_w);
         SVI_LAUNCH_CHECK();
     }
@@ -2467,9 +2474,27 @@ svi_status ensure_pool(svi_vae* h, long max_elems) {
     if (h->pool) { SVI_CHECK_HIP(hipFree(h->pool)); h->pool = nullptr; }
     hipError_t e = hipMalloc((void**)&h->pool, slot * nslots);
     if (e != hipSuccess) { svi_set_error("hipMalloc(%zu B VAE activation pool) failed: %s", slot * nslots, hipGetErrorString(e)); return SVI_ERR_OOM; }
-    h->slot_bytes = slot; h->nslots = nslots; h->pool_bytes = slot * nslots;
+    h->slot_bytes = slot; h->nslots = nslots;
     h->slot_used.assign(nslots, 0);
     return SVI_OK;
+}
+
+// The pool is sized by a dry walk of the very code path that then runs: `walk` runs once with h->dry set (nothing is allocated or
+// launched, alloc_t records the largest tensor) and the pool is made to hold slots of that size.  The flag is cleared whatever the
+// walk returns, so a failing dry walk cannot leave a handle on which every later call does nothing and reports success.  This is the
+// only function that sets h->dry.
+template <class Walk> svi_status size_pool(svi_vae* h, Walk walk) {
+    h->dry = true; h->dry_max = 0;
+    const svi_status dry = walk();
+    h->dry = false;
+    SVI_TRY(dry);
+    return ensure_pool(h, h->dry_max);
+}
+// size the pool by `walk`, then run it for real on an empty pool
+template <class Walk> svi_status sized_run(svi_vae* h, Walk walk) {
+    SVI_TRY(size_pool(h, walk));
+    h->slot_used.assign(h->nslots, 0);
+    return walk();
 }
 
 svi_status check_bound(svi_vae* h) {
@@ -2554,7 +2579,9 @@ extern "C" svi_status svi_vae_bind_weight(svi_vae* h, const char* name, const vo
         hipError_t e = hipMalloc((void**)&cw.packed, n * 4);
         if (e != hipSuccess) { svi_set_error("hipMalloc(packed VAE weight) failed: %s", hipGetErrorString(e)); return SVI_ERR_OOM; }
     }
-    hipLaunchKernelGGL(pack_weight_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, cw.w_user, cw.packed, cw.Cout, cw.Cin, taps, cw.ldw);
+    dim3 grid;
+    SVI_TRY(grid_256((long)n, name, &grid));
+    hipLaunchKernelGGL(pack_weight_kernel, grid, dim3(256), 0, 0, cw.w_user, cw.packed, cw.Cout, cw.Cin, taps, cw.ldw);
     const bool narrow_head = cw.Cout <= 32 && cw.kh == 3 && cw.kw == 3 && cw.Cin % 32 == 0;       // conv_dma2h_kernel<1> (two-term fp16 form on the producer's planes)
     if (cw.Cout >= 64 || narrow_head) {               // layers wide enough for conv_igemm_x3_kernel get the three-term bf16 form and the two-term fp16 form
         cw.ldw3 = (cw.Cin + 31) / 32 * 32;
@@ -2563,7 +2590,9 @@ extern "C" svi_status svi_vae_bind_weight(svi_vae* h, const char* name, const vo
             hipError_t e3 = hipMalloc((void**)&cw.packed3, 3 * n3 * 2);
             if (e3 != hipSuccess) { svi_set_error("hipMalloc(split VAE weight) failed: %s", hipGetErrorString(e3)); return SVI_ERR_OOM; }
         }
-        hipLaunchKernelGGL(pack_weight_x3_kernel, dim3((unsigned)((n3 + 255) / 256)), dim3(256), 0, 0, cw.w_user, cw.packed3, cw.Cout, cw.Cin, taps, cw.ldw3);
+        dim3 grid3;
+        SVI_TRY(grid_256((long)n3, name, &grid3));
+        hipLaunchKernelGGL(pack_weight_x3_kernel, grid3, dim3(256), 0, 0, cw.w_user, cw.packed3, cw.Cout, cw.Cin, taps, cw.ldw3);
         if (!cw.packed2h) {
             hipError_t e2 = hipMalloc((void**)&cw.packed2h, 2 * n3 * 2);
             if (e2 == hipSuccess) e2 = hipMalloc((void**)&cw.w2_scale, (size_t)2 * cw.Cout * 4);
@@ -2576,10 +2605,11 @@ extern "C" svi_status svi_vae_bind_weight(svi_vae* h, const char* name, const vo
                 if (eu != hipSuccess) { svi_set_error("hipMalloc(upsample phase weights) failed: %s", hipGetErrorString(eu)); return SVI_ERR_OOM; }
             }
             const size_t nt = (size_t)4 * 4 * cw.Cout * cw.ldw3;
-            hipLaunchKernelGGL(pack_weight_up_x3_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, 0, cw.w_user, cw.packed3_up, cw.Cout, cw.Cin, cw.ldw3);
+            SVI_TRY(grid_256((long)nt, name, &grid));
+            hipLaunchKernelGGL(pack_weight_up_x3_kernel, grid, dim3(256), 0, 0, cw.w_user, cw.packed3_up, cw.Cout, cw.Cin, cw.ldw3);
         }
         hipLaunchKernelGGL(weight_row_scale_kernel, dim3(cw.Cout), dim3(256), 0, 0, cw.w_user, cw.w2_scale, cw.w2_scale + cw.Cout, (long)cw.Cin * taps);
-        hipLaunchKernelGGL(pack_weight_x2h_kernel, dim3((unsigned)((n3 + 255) / 256)), dim3(256), 0, 0, cw.w_user, cw.w2_scale, cw.packed2h, cw.Cout, cw.Cin, taps, cw.ldw3);
+        hipLaunchKernelGGL(pack_weight_x2h_kernel, grid3, dim3(256), 0, 0, cw.w_user, cw.w2_scale, cw.packed2h, cw.Cout, cw.Cin, taps, cw.ldw3);
     }
     SVI_LAUNCH_CHECK();
     h->pack_pending = true;
@@ -2613,12 +2643,7 @@ extern "C" svi_status svi_vae_decode(svi_vae* h, const float* latents, float* vi
     SVI_REQUIRE_DEVICE(h);
     SVI_TRY(vae_prepare(h));
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    h->dry = true; h->dry_max = 0;
-    SVI_TRY(decode_graph(h, latents, video, T, hh, ww, st));
-    h->dry = false;
-    SVI_TRY(ensure_pool(h, h->dry_max));
-    h->slot_used.assign(h->nslots, 0);
-    return decode_graph(h, latents, video, T, hh, ww, st);
+    return sized_run(h, [&] { return decode_graph(h, latents, video, T, hh, ww, nullptr, 0, 0, st); });
 }
 
 // out24 = {owned h0, h1, w0, w1 | halo of stages 0-3 | stage 0 rectangle h0, h1, w0, w1 | stage 1 | stage 2 | stage 3}.  Host arithmetic only.
@@ -2626,8 +2651,7 @@ extern "C" svi_status svi_vae_split_plan(int32_t hh, int32_t ww, int32_t parts_h
     SVI_REQUIRE(out24, "svi_vae_split_plan: null argument");
     SplitPlan pl{};
     SVI_TRY(split_plan(hh, ww, parts_h, parts_w, part, &pl));
-    for (int k = 0; k < 4; ++k) { out24[k] = pl.own[k]; out24[4 + k] = pl.halo[k]; }
-    for (int s = 0; s < 4; ++s) for (int k = 0; k < 4; ++k) out24[8 + 4 * s + k] = pl.pad[s][k];
+    plan_to_flat(pl, out24);
     return SVI_OK;
 }
 
@@ -2637,13 +2661,7 @@ static svi_status decode_with_plan(svi_vae* h, const float* latents, float* vide
                 "svi_vae_decode_part: video pitches %d rows x %d elements are smaller than the owned window %d x %d", video_ld_h, video_ld_w,
                 8 * (pl.own[1] - pl.own[0]), 8 * (pl.own[3] - pl.own[2]));
     SVI_TRY(vae_prepare(h));
-    h->dry = true; h->dry_max = 0;
-    const svi_status dry = decode_part_graph(h, latents, video, T, hh, ww, pl, video_ld_h, video_ld_w, st);
-    h->dry = false;
-    SVI_TRY(dry);
-    SVI_TRY(ensure_pool(h, h->dry_max));
-    h->slot_used.assign(h->nslots, 0);
-    return decode_part_graph(h, latents, video, T, hh, ww, pl, video_ld_h, video_ld_w, st);
+    return sized_run(h, [&] { return decode_graph(h, latents, video, T, hh, ww, &pl, video_ld_h, video_ld_w, st); });
 }
 
 extern "C" svi_status svi_vae_decode_part(svi_vae* h, const float* latents, float* video, int32_t T, int32_t hh, int32_t ww, int32_t parts_h, int32_t parts_w,
@@ -2660,9 +2678,7 @@ extern "C" svi_status svi_vae_decode_planned(svi_vae* h, const float* latents, f
                                              int32_t video_ld_h, int32_t video_ld_w, svi_stream stream) {
     SVI_REQUIRE(h && latents && video && plan24 && T > 0 && hh > 0 && ww > 0, "svi_vae_decode_planned: bad argument");
     SVI_REQUIRE_DEVICE(h);
-    SplitPlan pl{};
-    for (int k = 0; k < 4; ++k) { pl.own[k] = plan24[k]; pl.halo[k] = plan24[4 + k]; }
-    for (int s = 0; s < 4; ++s) for (int k = 0; k < 4; ++k) pl.pad[s][k] = plan24[8 + 4 * s + k];
+    const SplitPlan pl = plan_from_flat<SplitPlan>(plan24);
     SVI_TRY(split_plan_check(pl, hh, ww));
     return decode_with_plan(h, latents, video, T, hh, ww, pl, video_ld_h, video_ld_w, reinterpret_cast<hipStream_t>(stream));
 }
@@ -2674,12 +2690,7 @@ extern "C" svi_status svi_vae_encode(svi_vae* h, const float* video, float* late
     SVI_REQUIRE((T - 1) % 4 == 0 && H % 8 == 0 && W % 8 == 0, "svi_vae_encode: needs T = 1+4k frames and H, W multiples of 8 (got %d, %d, %d)", T, H, W);
     SVI_TRY(vae_prepare(h));
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    h->dry = true; h->dry_max = 0;
-    SVI_TRY(encode_graph(h, video, latents, T, H, W, st));
-    h->dry = false;
-    SVI_TRY(ensure_pool(h, h->dry_max));
-    h->slot_used.assign(h->nslots, 0);
-    return encode_graph(h, video, latents, T, H, W, st);
+    return sized_run(h, [&] { return encode_graph(h, video, latents, T, H, W, st); });
 }
 
 // out34 = {owned h0, h1, w0, w1 | reach (top/left, bottom/right) at the video, stages 0-3 | rectangle (h0, h1, w0, w1) at the video, stages 0-3}.
@@ -2688,9 +2699,7 @@ extern "C" svi_status svi_vae_encode_split_plan(int32_t hh, int32_t ww, int32_t 
     SVI_REQUIRE(out34, "svi_vae_encode_split_plan: null argument");
     EncSplitPlan pl{};
     SVI_TRY(encode_split_plan(hh, ww, parts_h, parts_w, part, &pl));
-    for (int k = 0; k < 4; ++k) out34[k] = pl.own[k];
-    for (int k = 0; k < 5; ++k) { out34[4 + 2 * k] = pl.reach[k][0]; out34[5 + 2 * k] = pl.reach[k][1]; }
-    for (int k = 0; k < 5; ++k) for (int m = 0; m < 4; ++m) out34[14 + 4 * k + m] = pl.rect[k][m];
+    plan_to_flat(pl, out34);
     return SVI_OK;
 }
 
@@ -2699,13 +2708,7 @@ static svi_status encode_with_plan(svi_vae* h, const float* video, float* feat_o
                 ld_h, ld_w, pl.own[1] - pl.own[0], pl.own[3] - pl.own[2]);
     SVI_REQUIRE(reinterpret_cast<uintptr_t>(feat_out) % 16 == 0, "svi_vae_encode_part: feat_out must be 16-byte aligned");
     SVI_TRY(vae_prepare(h));
-    h->dry = true; h->dry_max = 0;
-    const svi_status dry = encode_part_graph(h, video, feat_out, T, H, W, pl, ld_h, ld_w, st);
-    h->dry = false;
-    SVI_TRY(dry);
-    SVI_TRY(ensure_pool(h, h->dry_max));
-    h->slot_used.assign(h->nslots, 0);
-    return encode_part_graph(h, video, feat_out, T, H, W, pl, ld_h, ld_w, st);
+    return sized_run(h, [&] { return encode_part_graph(h, video, feat_out, T, H, W, pl, ld_h, ld_w, st); });
 }
 
 extern "C" svi_status svi_vae_encode_part(svi_vae* h, const float* video, float* feat_out, int32_t T, int32_t H, int32_t W, int32_t parts_h, int32_t parts_w,
@@ -2723,10 +2726,7 @@ extern "C" svi_status svi_vae_encode_planned(svi_vae* h, const float* video, flo
     SVI_REQUIRE(h && video && feat_out && plan34 && T > 0 && H > 0 && W > 0, "svi_vae_encode_planned: bad argument");
     SVI_REQUIRE_DEVICE(h);
     SVI_REQUIRE((T - 1) % 4 == 0 && H % 8 == 0 && W % 8 == 0, "svi_vae_encode_planned: needs T = 1+4k frames and H, W multiples of 8 (got %d, %d, %d)", T, H, W);
-    EncSplitPlan pl{};
-    for (int k = 0; k < 4; ++k) pl.own[k] = plan34[k];
-    for (int k = 0; k < 5; ++k) { pl.reach[k][0] = plan34[4 + 2 * k]; pl.reach[k][1] = plan34[5 + 2 * k]; }
-    for (int k = 0; k < 5; ++k) for (int m = 0; m < 4; ++m) pl.rect[k][m] = plan34[14 + 4 * k + m];
+    const EncSplitPlan pl = plan_from_flat<EncSplitPlan>(plan34);
     SVI_TRY(encode_split_plan_check(pl, H / 8, W / 8));
     return encode_with_plan(h, video, feat_out, T, H, W, pl, ld_h, ld_w, reinterpret_cast<hipStream_t>(stream));
 }
@@ -2736,13 +2736,7 @@ extern "C" svi_status svi_vae_encode_tail(svi_vae* h, const float* feat, float* 
     SVI_REQUIRE_DEVICE(h);
     SVI_TRY(vae_prepare(h));
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    h->dry = true; h->dry_max = 0;
-    const svi_status dry = encode_tail_graph(h, feat, latents, Tl, hh, ww, st);
-    h->dry = false;
-    SVI_TRY(dry);
-    SVI_TRY(ensure_pool(h, h->dry_max));
-    h->slot_used.assign(h->nslots, 0);
-    return encode_tail_graph(h, feat, latents, Tl, hh, ww, st);
+    return sized_run(h, [&] { return encode_tail_graph(h, feat, latents, Tl, hh, ww, st); });
 }
 
 // ---- tiled paths ------------------------------------------------------------------------------------------------------------
@@ -2770,6 +2764,43 @@ svi_status ensure_blend(svi_vae* h, size_t bytes) {
     h->blend_bytes = bytes;
     return SVI_OK;
 }
+// The tile walk of both tiled paths (vae:643-693 / :696-744).  The input is [.., Hf, Wf], tile size and stride are in its pixels; the
+// output `out` is `planes` planes 8x finer (to_pixels: latents -> video) or 8x coarser (video -> latents).  Sizes the blend weights and,
+// by the largest (first) tile, the pool; zeroes both accumulators; runs tile(th, tw) for every tile with h->win set, on an empty pool;
+// then divides the blended values by the blended weights, clamping a video (the reference clamps after the blend).
+template <class Tile>
+svi_status tile_walk(svi_vae* h, int Hf, int Wf, int size_h, int size_w, int stride_h, int stride_w, bool to_pixels, float* out, long planes, hipStream_t st, Tile tile) {
+    auto scaled = [&](int v) { return to_pixels ? v * 8 : v / 8; };
+    const char* unit = to_pixels ? "" : "latent ";
+    const int Ho = scaled(Hf), Wo = scaled(Wf);
+    SVI_TRY(ensure_blend(h, (size_t)Ho * Wo * 4));
+    const auto hs = tile_starts(Hf, size_h, stride_h), wsv = tile_starts(Wf, size_w, stride_w);
+    SVI_TRY(size_pool(h, [&] { return tile(std::min(size_h, Hf), std::min(size_w, Wf)); }));
+    SVI_CHECK_HIP(hipMemsetAsync(out, 0, (size_t)planes * Ho * Wo * 4, st));
+    SVI_CHECK_HIP(hipMemsetAsync(h->blend_w, 0, (size_t)Ho * Wo * 4, st));
+    for (auto& a : hs) {
+        for (auto& b : wsv) {
+            TileWin w{};
+            w.Hf = Hf; w.Wf = Wf; w.h0 = a.first; w.w0 = b.first;
+            w.th = std::min(a.second, Hf) - a.first; w.tw = std::min(b.second, Wf) - b.first;
+            w.oHf = Ho; w.oWf = Wo; w.oh0 = scaled(a.first); w.ow0 = scaled(b.first);
+            w.lb = a.first == 0; w.rb = a.second >= Hf; w.tb = b.first == 0; w.bb = b.second >= Wf;
+            w.border_h = scaled(size_h - stride_h); w.border_w = scaled(size_w - stride_w);
+            // the reference writes a `border`-long ramp into the tile's mask: a clipped tile shorter than the ramp is an error there too
+            if ((!w.lb || !w.rb) && scaled(w.th) < w.border_h) { svi_set_error("tile of %d %srows is shorter than the %d-row blend border", scaled(w.th), unit, w.border_h); return SVI_ERR_INVALID; }
+            if ((!w.tb || !w.bb) && scaled(w.tw) < w.border_w) { svi_set_error("tile of %d %scolumns is shorter than the %d-column blend border", scaled(w.tw), unit, w.border_w); return SVI_ERR_INVALID; }
+            h->slot_used.assign(h->nslots, 0);
+            WinScope ws_(h, &w);
+            SVI_TRY(tile(w.th, w.tw));
+        }
+    }
+    const long plane = (long)Ho * Wo;
+    dim3 grid;
+    SVI_TRY(grid_256(planes * plane, "VAE tiled path: the output", &grid));
+    hipLaunchKernelGGL(tile_finalize_kernel, grid, dim3(256), 0, st, out, h->blend_w, planes, plane, to_pixels ? 1 : 0);
+    SVI_LAUNCH_CHECK();
+    return SVI_OK;
+}
 }  // namespace
 
 extern "C" svi_status svi_vae_tiled_decode(svi_vae* h, const float* latents, float* video, int32_t T, int32_t hh, int32_t ww,
@@ -2780,38 +2811,8 @@ extern "C" svi_status svi_vae_tiled_decode(svi_vae* h, const float* latents, flo
                 "svi_vae_tiled_decode: tile_size / tile_stride must be positive with stride <= size");
     SVI_TRY(vae_prepare(h));
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int f = 8, To = 4 * T - 3, Ho = hh * f, Wo = ww * f;
-    SVI_TRY(ensure_blend(h, (size_t)Ho * Wo * 4));
-    const auto hs = tile_starts(hh, size_h, stride_h), wsv = tile_starts(ww, size_w, stride_w);
-    // the pool is sized by the largest (first) tile
-    const int mh = std::min(size_h, hh), mw = std::min(size_w, ww);
-    h->dry = true; h->dry_max = 0;
-    SVI_TRY(decode_graph(h, latents, video, T, mh, mw, st));
-    h->dry = false;
-    SVI_TRY(ensure_pool(h, h->dry_max));
-    SVI_CHECK_HIP(hipMemsetAsync(video, 0, (size_t)3 * To * Ho * Wo * 4, st));
-    SVI_CHECK_HIP(hipMemsetAsync(h->blend_w, 0, (size_t)Ho * Wo * 4, st));
-    svi_status rc = SVI_OK;
-    for (auto& a : hs) {
-        for (auto& b : wsv) {
-            TileWin w{};
-            w.Hf = hh; w.Wf = ww; w.h0 = a.first; w.w0 = b.first;
-            w.th = std::min(a.second, hh) - a.first; w.tw = std::min(b.second, ww) - b.first;
-            w.oHf = Ho; w.oWf = Wo; w.oh0 = a.first * f; w.ow0 = b.first * f;
-            w.lb = a.first == 0; w.rb = a.second >= hh; w.tb = b.first == 0; w.bb = b.second >= ww;
-            w.border_h = (size_h - stride_h) * f; w.border_w = (size_w - stride_w) * f;
-            // the reference writes a `border`-long ramp into the tile's mask: a clipped tile shorter than the ramp is an error there too
-            if ((!w.lb || !w.rb) && w.th * f < w.border_h) { svi_set_error("tile of %d rows is shorter than the %d-row blend border", w.th * f, w.border_h); return SVI_ERR_INVALID; }
-            if ((!w.tb || !w.bb) && w.tw * f < w.border_w) { svi_set_error("tile of %d columns is shorter than the %d-column blend border", w.tw * f, w.border_w); return SVI_ERR_INVALID; }
-            h->slot_used.assign(h->nslots, 0);
-            { WinScope ws_(h, &w); rc = decode_graph(h, latents, video, T, w.th, w.tw, st); }
-            if (rc != SVI_OK) return rc;
-        }
-    }
-    const long plane = (long)Ho * Wo, planes = 3L * To;
-    hipLaunchKernelGGL(tile_finalize_kernel, dim3((unsigned)((planes * plane + 255) / 256)), dim3(256), 0, st, video, h->blend_w, planes, plane, 1);
-    SVI_LAUNCH_CHECK();
-    return SVI_OK;
+    return tile_walk(h, hh, ww, size_h, size_w, stride_h, stride_w, /*to_pixels=*/true, video, 3L * (4 * T - 3), st,
+                     [&](int th, int tw) { return decode_graph(h, latents, video, T, th, tw, nullptr, 0, 0, st); });
 }
 
 extern "C" svi_status svi_vae_tiled_encode(svi_vae* h, const float* video, float* latents, int32_t T, int32_t H, int32_t W,
@@ -2824,36 +2825,8 @@ extern "C" svi_status svi_vae_tiled_encode(svi_vae* h, const float* video, float
                 "svi_vae_tiled_encode: tile_size / tile_stride are in pixels, multiples of 8, stride <= size");
     SVI_TRY(vae_prepare(h));
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int f = 8, To = (T + 3) / 4, Ho = H / f, Wo = W / f;
-    SVI_TRY(ensure_blend(h, (size_t)Ho * Wo * 4));
-    const auto hs = tile_starts(H, size_h, stride_h), wsv = tile_starts(W, size_w, stride_w);
-    const int mh = std::min(size_h, H), mw = std::min(size_w, W);
-    h->dry = true; h->dry_max = 0;
-    SVI_TRY(encode_graph(h, video, latents, T, mh, mw, st));
-    h->dry = false;
-    SVI_TRY(ensure_pool(h, h->dry_max));
-    SVI_CHECK_HIP(hipMemsetAsync(latents, 0, (size_t)16 * To * Ho * Wo * 4, st));
-    SVI_CHECK_HIP(hipMemsetAsync(h->blend_w, 0, (size_t)Ho * Wo * 4, st));
-    svi_status rc = SVI_OK;
-    for (auto& a : hs) {
-        for (auto& b : wsv) {
-            TileWin w{};
-            w.Hf = H; w.Wf = W; w.h0 = a.first; w.w0 = b.first;
-            w.th = std::min(a.second, H) - a.first; w.tw = std::min(b.second, W) - b.first;
-            w.oHf = Ho; w.oWf = Wo; w.oh0 = a.first / f; w.ow0 = b.first / f;
-            w.lb = a.first == 0; w.rb = a.second >= H; w.tb = b.first == 0; w.bb = b.second >= W;
-            w.border_h = (size_h - stride_h) / f; w.border_w = (size_w - stride_w) / f;
-            if ((!w.lb || !w.rb) && w.th / f < w.border_h) { svi_set_error("tile of %d latent rows is shorter than the %d-row blend border", w.th / f, w.border_h); return SVI_ERR_INVALID; }
-            if ((!w.tb || !w.bb) && w.tw / f < w.border_w) { svi_set_error("tile of %d latent columns is shorter than the %d-column blend border", w.tw / f, w.border_w); return SVI_ERR_INVALID; }
-            h->slot_used.assign(h->nslots, 0);
-            { WinScope ws_(h, &w); rc = encode_graph(h, video, latents, T, w.th, w.tw, st); }
-            if (rc != SVI_OK) return rc;
-        }
-    }
-    const long plane = (long)Ho * Wo, planes = 16L * To;
-    hipLaunchKernelGGL(tile_finalize_kernel, dim3((unsigned)((planes * plane + 255) / 256)), dim3(256), 0, st, latents, h->blend_w, planes, plane, 0);
-    SVI_LAUNCH_CHECK();
-    return SVI_OK;
+    return tile_walk(h, H, W, size_h, size_w, stride_h, stride_w, /*to_pixels=*/false, latents, 16L * ((T + 3) / 4), st,
+                     [&](int th, int tw) { return encode_graph(h, video, latents, T, th, tw, st); });
 }
 
 

@@ -144,6 +144,22 @@ def test_one_part_is_todays_encode(vae):
     assert torch.equal(v.encode_tail(v.encode_part(vid, (1, 1), 0)), want)
 
 
+def test_one_part_at_other_pitches_is_the_whole_front(vae):
+    """One part into a feature buffer 3 rows and 5 columns larger than the map: the window holds the bits of part 0 written into a tight
+    buffer, nothing outside it is written, and the tail of the tight buffer is the whole encode bit for bit (the part form of the encoder
+    front with a trivial plan is the whole front)."""
+    v, _ = vae
+    vid, want = whole_encode(v, 713, (3, 5, 40, 56))
+    tl, hh, ww = want.shape[1], 40 // 8, 56 // 8
+    tight = v.encode_part(vid, (1, 1), 0)
+    assert tuple(tight.shape) == (tl, hh, ww, 384)
+    padded = torch.full((tl, hh + 3, ww + 5, 384), 7.5, device="cuda")
+    assert v.encode_part(vid, (1, 1), 0, out=padded) is padded
+    assert torch.equal(padded[:, :hh, :ww], tight)
+    assert bool((padded[:, hh:] == 7.5).all()) and bool((padded[:, :, ww:] == 7.5).all())
+    assert torch.equal(v.encode_tail(tight), want)
+
+
 def test_refusals(vae):
     v, _ = vae
     vid, _ = whole_encode(v, 713, (3, 5, 40, 56))

@@ -139,6 +139,19 @@ def test_one_part_is_todays_decode(vae):
     assert torch.equal(v.decode_part(z, (1, 1), 0), want)
 
 
+def test_one_part_at_other_pitches_is_the_whole_decode(vae):
+    """One part into a buffer 3 rows and 5 columns larger than the frame: the pitches are not the frame's, so the call runs the part form of
+    the decoder walk (trivial plan: every stage's rectangle is the whole activation) instead of handing over to the whole decode, and must
+    give the whole decode's bits; nothing outside the window is written."""
+    v, _ = vae
+    z, want = whole_decode(v, 703, (16, 2, 5, 7))
+    H, W = want.shape[2:]
+    padded = torch.full((3, want.shape[1], H + 3, W + 5), 7.5, device="cuda")
+    assert v.decode_part(z, (1, 1), 0, out=padded) is padded
+    assert torch.equal(padded[:, :, :H, :W], want)
+    assert bool((padded[:, :, H:] == 7.5).all()) and bool((padded[:, :, :, W:] == 7.5).all())
+
+
 def test_refusals(vae):
     v, _ = vae
     z, _ = whole_decode(v, 703, (16, 2, 5, 7))

@@ -164,6 +164,28 @@ svi_status svi_dit_audio_slot(svi_dit* h, int32_t slot /* 0 or 1 */, const void*
 svi_status svi_dit_forward_talk3(svi_dit* h, const void* x, const float* timestep, const void* context_cond, const void* context_uncond,
                                  const void* clip_feature, const void* y, const void* add_condition, void* out_cond, void* out_uncond,
                                  void* out_drop_text, int32_t T, int32_t H, int32_t W, int32_t Lc, svi_stream stream);
+/* The clip boundary of a talk STREAM (additive in v13): the clip's audio windows cut on the device out of the whole stream's audio embedding.
+ *
+ * svi_audio_windows (the operator seam): emb [N, R] — one row per audio frame of the stream, fp32 (as the reference holds the wav2vec2 output) or bf16,
+ * R = blocks x channels (12 x 768 in the real model; any R % 8 == 0) — is read for the clip that starts at audio frame `start` and has T_latent latent
+ * frames (4 (T_latent - 1) + 1 video frames, window 5).  The row of (video frame f, window position w) is clamp(start + f + (w - 2), 0, N - 1):
+ *   first_out  bf16 [1, 5, R]             video frame 0's five window rows                                            (audio_embed_tuple[0])
+ *   latter_out bf16 [T_latent - 1, 8, R]  latent frame t = video frames 1 + 4t .. 4 + 4t: positions 0, 1, 2 of the first, the centre (2) of the two
+ *                                         middle ones, positions 2, 3, 4 of the last; may be NULL when T_latent == 1 (audio_embed_tuple[1])
+ * = SVITalkVideoPipeline.get_audio_embedding + preprocess_audio + .to(bfloat16) (pipelines/svi_video_talk.py:412-446): a clamped gather and one
+ * round-to-nearest-even, so the result is defined bit for bit.  One launch, 16-byte accesses (operands 16-byte aligned).
+ *
+ * svi_dit_audio_slot_windows cuts the windows of the model's width (R = 12 x 768) into buffers slot `slot` owns and re-projects the slot from there
+ * with svi_dit_audio_slot's launches — the bits of svi_dit_audio_slot on host-built windows.  Same rules as svi_dit_audio_slot: a slot that is staged
+ * for T_latent frames is rewritten in place (nothing is allocated, svi_dit_generation does not move: legal between replays of a captured talk step);
+ * otherwise it is (re)allocated (refused while the stream is being captured).  emb is read by the work this call enqueues and is not borrowed.
+ *
+ * Both refuse, with a message and before any launch: a NULL emb, N < 1, T_latent < 1, start < 0, a dtype other than fp32 / bf16; svi_audio_windows
+ * also an R that is not a positive multiple of 8 or a NULL output. */
+svi_status svi_audio_windows(const void* emb, svi_dtype dtype, int32_t N, int32_t R, int32_t start, int32_t T_latent, void* first_out,
+                             void* latter_out, svi_stream stream);
+svi_status svi_dit_audio_slot_windows(svi_dit* h, int32_t slot /* 0 or 1 */, const void* emb, svi_dtype dtype, int32_t N, int32_t start,
+                                      int32_t T_latent, svi_stream stream);
 /* The talk step with TeaCache (additive in v13): svi_dit_forward_talk3 plus svi_dit_forward_tea's modes, one per branch, and one residual bf16 [1, L, dim]
  * per branch.  Per branch k = cond, uncond, drop_text:
  *   0: run the blocks; residual_k is ignored (may be NULL).

@@ -609,3 +609,18 @@ extern "C" svi_status svi_cfg3_step(void* latents, const void* cond, const void*
     return svi_launch_cfg3_step(reinterpret_cast<bf16*>(latents), reinterpret_cast<const bf16*>(cond), reinterpret_cast<const bf16*>(uncond),
                                 reinterpret_cast<const bf16*>(drop_text), n, s_text, s_audio, dsigma, reinterpret_cast<hipStream_t>(stream));
 }
+
+// The talk stream's clip audio windows, cut on the device (svi_launch_audio_windows): the operator seam of svi_dit_audio_slot_windows.
+extern "C" svi_status svi_audio_windows(const void* emb, svi_dtype dtype, int32_t N, int32_t R, int32_t start, int32_t T_latent, void* first_out,
+                                        void* latter_out, svi_stream stream) {
+    SVI_REQUIRE(emb, "svi_audio_windows: emb is NULL");
+    SVI_REQUIRE(dtype == SVI_F32 || dtype == SVI_BF16, "svi_audio_windows: emb must be fp32 or bf16 (dtype %d)", (int)dtype);
+    SVI_REQUIRE(N >= 1, "svi_audio_windows: N = %d audio frames (at least one)", N);
+    SVI_REQUIRE(T_latent >= 1, "svi_audio_windows: T_latent = %d (at least one latent frame)", T_latent);
+    SVI_REQUIRE(R > 0 && R % 8 == 0, "svi_audio_windows: R = %d must be a positive multiple of 8", R);
+    SVI_REQUIRE(start >= 0, "svi_audio_windows: start = %d is negative", start);
+    SVI_REQUIRE(first_out && (T_latent == 1 || latter_out), "svi_audio_windows: NULL output");
+    if (svi_current_device() < 0) return SVI_ERR_HIP;
+    return svi_launch_audio_windows(emb, dtype == SVI_F32, N, R, start, T_latent, reinterpret_cast<bf16*>(first_out), reinterpret_cast<bf16*>(latter_out),
+                                    reinterpret_cast<hipStream_t>(stream));
+}

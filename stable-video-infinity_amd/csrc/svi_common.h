@@ -321,6 +321,9 @@ svi_status svi_launch_cfg3_step(bf16* lat, const bf16* cond, const bf16* uncond,
 svi_status svi_launch_video_to_u8(const float* video, unsigned char* out, long thw, hipStream_t st);
 svi_status svi_launch_u8_to_video(const unsigned char* frames, float* out, int n, long hw, hipStream_t st);
 svi_status svi_launch_sub_bf16(bf16* out, const bf16* a, const bf16* b, int64_t n, hipStream_t st);
+// the talk stream's clip audio windows cut from the whole stream's embedding emb [N, R] (fp32 when f32, else bf16): first [5, R], latter [T - 1, 8, R] bf16
+// (svi_elementwise.hip; R % 8 == 0, operands 16-byte aligned; latter may be null when T == 1)
+svi_status svi_launch_audio_windows(const void* emb, bool f32, int N, int R, int start, int T, bf16* first, bf16* latter, hipStream_t st);
 // out_k = modulate(LayerNorm(bf16(x + res_k))) for one or two residuals over the same rows of x (the TeaCache skip step of a CFG pair); res_b / out_b may be null
 svi_status svi_launch_add_ln_mod_pair(const bf16* x, const bf16* res_a, const bf16* res_b, bf16* out_a, bf16* out_b, int rows, int dim, float eps,
                                       const float* shift, const float* scale1p, hipStream_t st);

@@ -94,6 +94,7 @@ struct AudSlot {
     bool staged = false;            // false after a weight was bound: the projections were made with the old values
     int ld = 0;
     bf16 *H0 = nullptr, *H1 = nullptr, *P3 = nullptr, *AUD = nullptr;
+    bf16 *WF = nullptr, *WL = nullptr;      // the slot's own audio windows (svi_dit_audio_slot_windows cuts them here)
     std::vector<bf16*> K, VT;
 };
 struct AudKV { const bf16* K; const bf16* VT; int ld; };      // one block's projected audio keys / values of a staged slot
@@ -1177,6 +1178,50 @@ extern "C" svi_status svi_dit_set_audio(svi_dit* h, const void* audio_first, con
 
 // One clip's audio windows -> a slot: AudioProjModel once, then every block's audio K / V^T (include/svi_hip.h).  A slot that holds this frame count is
 // rewritten where it stands (the clip boundary of a resident loop: no address and no generation moves); otherwise it is (re)allocated.
+// slot_ensure: the slot's buffers for f latent frames — the projections and the slot's own copy of the windows (WF [5, 12 * 768], WL [f - 1, 8, 12 * 768]:
+// where svi_dit_audio_slot_windows cuts them; svi_dit_audio_slot reads the caller's instead).
+#define SVI_AUD_ROW (12 * SVI_AUD_DIM)       // one audio frame's embedding: 12 wav2vec2 blocks x 768 channels
+static svi_status slot_ensure(svi_dit* h, int slot, int f, hipStream_t st, const char* who) {
+    AudSlot& s = h->aud_slot[slot];
+    const int nl = h->cfg.num_layers;
+    const size_t D = h->cfg.dim, na = (size_t)f * SVI_AUD_TOK;
+    if (!s.base || s.frames != f) {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) {
+            svi_set_error("%s: slot %d must be allocated while the stream is being captured: stage this frame count once before the capture", who, slot);
+            return SVI_ERR_INVALID;
+        }
+        (void)hipGetLastError();
+        const int ld = (int)((na + 7) / 8 * 8);
+        size_t off = 0;
+        auto take = [&](size_t bytes) { size_t o = off; off += al(bytes); return o; };
+        const size_t oh0 = take((size_t)f * 512 * 2), oh1 = take((size_t)f * 512 * 2), op3 = take(na * SVI_AUD_DIM * 2), oaud = take(na * SVI_AUD_DIM * 2);
+        std::vector<size_t> ok(nl), ov(nl);
+        for (int l = 0; l < nl; ++l) { ok[l] = take(na * D * 2); ov[l] = take(D * ld * 2); }
+        const size_t owf = take((size_t)5 * SVI_AUD_ROW * 2), owl = take((size_t)(f - 1) * 8 * SVI_AUD_ROW * 2);
+        if (s.base) { SVI_CHECK_HIP(hipFree(s.base)); s = AudSlot{}; }
+        char* base = nullptr;
+        hipError_t e = hipMalloc((void**)&base, off);
+        if (e != hipSuccess) { svi_set_error("hipMalloc(%zu B audio slot %d) failed: %s", off, slot, hipGetErrorString(e)); return SVI_ERR_OOM; }
+        s.base = base; s.bytes = off; s.frames = f; s.ld = ld;
+        SVI_CHECK_HIP(hipMemsetAsync(base, 0, off, st));
+        auto P = [&](size_t o) { return reinterpret_cast<bf16*>(base + o); };
+        s.H0 = P(oh0); s.H1 = P(oh1); s.P3 = P(op3); s.AUD = P(oaud); s.WF = P(owf); s.WL = P(owl);
+        s.K.resize(nl); s.VT.resize(nl);
+        for (int l = 0; l < nl; ++l) { s.K[l] = P(ok[l]); s.VT[l] = P(ov[l]); }
+        ++h->generation;
+    } else if (!s.staged) ++h->generation;          // dropped by a re-bind: staged anew (the buffers are reused; a graph made before the re-bind is stale anyway)
+    return SVI_OK;
+}
+// project the windows at first / latter into the slot: the launches of an armed forward, so the bits are a forward's
+static svi_status slot_project(svi_dit* h, AudSlot& s, const bf16* first, const bf16* latter, hipStream_t st) {
+    const int f = s.frames, nl = h->cfg.num_layers, na = f * SVI_AUD_TOK;
+    s.staged = false;
+    SVI_TRY(project_audio(h, first, latter, f, s.H0, s.H1, s.P3, s.AUD, st));
+    for (int l = 0; l < nl; ++l) SVI_TRY(fill_block_audio_kv(h, l, s.AUD, na, s.K[l], s.VT[l], s.ld, st));
+    s.staged = true;
+    return SVI_OK;
+}
 extern "C" svi_status svi_dit_audio_slot(svi_dit* h, int32_t slot, const void* audio_first, const void* audio_latter, int32_t n_latter, svi_stream stream) {
     SVI_REQUIRE(h, "null handle");
     SVI_REQUIRE(slot == 0 || slot == 1, "svi_dit_audio_slot: slot %d (0 = the clip's audio, 1 = the null audio)", slot);
@@ -1191,38 +1236,30 @@ extern "C" svi_status svi_dit_audio_slot(svi_dit* h, int32_t slot, const void* a
     SVI_REQUIRE(((uintptr_t)audio_first % 16) == 0 && ((uintptr_t)audio_latter % 16) == 0, "svi_dit_audio_slot: audio windows must be 16-byte aligned");
     SVI_TRY(svi_dit_check_bound(h));
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int f = n_latter + 1, nl = h->cfg.num_layers;
-    const size_t D = h->cfg.dim, na = (size_t)f * SVI_AUD_TOK;
-    if (!s.base || s.frames != f) {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) {
-            svi_set_error("svi_dit_audio_slot: slot %d must be allocated while the stream is being captured: stage this frame count once before the capture", slot);
-            return SVI_ERR_INVALID;
-        }
-        (void)hipGetLastError();
-        const int ld = (int)((na + 7) / 8 * 8);
-        size_t off = 0;
-        auto take = [&](size_t bytes) { size_t o = off; off += al(bytes); return o; };
-        const size_t oh0 = take((size_t)f * 512 * 2), oh1 = take((size_t)f * 512 * 2), op3 = take(na * SVI_AUD_DIM * 2), oaud = take(na * SVI_AUD_DIM * 2);
-        std::vector<size_t> ok(nl), ov(nl);
-        for (int l = 0; l < nl; ++l) { ok[l] = take(na * D * 2); ov[l] = take(D * ld * 2); }
-        if (s.base) { SVI_CHECK_HIP(hipFree(s.base)); s = AudSlot{}; }
-        char* base = nullptr;
-        hipError_t e = hipMalloc((void**)&base, off);
-        if (e != hipSuccess) { svi_set_error("hipMalloc(%zu B audio slot %d) failed: %s", off, slot, hipGetErrorString(e)); return SVI_ERR_OOM; }
-        s.base = base; s.bytes = off; s.frames = f; s.ld = ld;
-        SVI_CHECK_HIP(hipMemsetAsync(base, 0, off, st));
-        auto P = [&](size_t o) { return reinterpret_cast<bf16*>(base + o); };
-        s.H0 = P(oh0); s.H1 = P(oh1); s.P3 = P(op3); s.AUD = P(oaud);
-        s.K.resize(nl); s.VT.resize(nl);
-        for (int l = 0; l < nl; ++l) { s.K[l] = P(ok[l]); s.VT[l] = P(ov[l]); }
-        ++h->generation;
-    } else if (!s.staged) ++h->generation;          // dropped by a re-bind: staged anew (the buffers are reused; a graph made before the re-bind is stale anyway)
+    SVI_TRY(slot_ensure(h, slot, n_latter + 1, st, "svi_dit_audio_slot"));
+    return slot_project(h, s, reinterpret_cast<const bf16*>(audio_first), reinterpret_cast<const bf16*>(audio_latter), st);
+}
+// The clip boundary of a talk stream: cut the clip's windows out of the whole stream's embedding into the slot's own window buffers (one launch,
+// svi_launch_audio_windows), then svi_dit_audio_slot's projection from there.  Same rules: in place for an unchanged frame count.
+extern "C" svi_status svi_dit_audio_slot_windows(svi_dit* h, int32_t slot, const void* emb, svi_dtype dtype, int32_t N, int32_t start, int32_t T_latent,
+                                                 svi_stream stream) {
+    SVI_REQUIRE(h, "null handle");
+    SVI_REQUIRE(slot == 0 || slot == 1, "svi_dit_audio_slot_windows: slot %d (0 = the clip's audio, 1 = the null audio)", slot);
+    SVI_REQUIRE(emb, "svi_dit_audio_slot_windows: emb is NULL");
+    SVI_REQUIRE(dtype == SVI_F32 || dtype == SVI_BF16, "svi_dit_audio_slot_windows: emb must be fp32 or bf16 (dtype %d)", (int)dtype);
+    SVI_REQUIRE(N >= 1, "svi_dit_audio_slot_windows: N = %d audio frames (at least one)", N);
+    SVI_REQUIRE(T_latent >= 1, "svi_dit_audio_slot_windows: T_latent = %d (at least one latent frame)", T_latent);
+    SVI_REQUIRE(start >= 0, "svi_dit_audio_slot_windows: start = %d is negative", start);
+    SVI_REQUIRE(((uintptr_t)emb % 16) == 0, "svi_dit_audio_slot_windows: emb must be 16-byte aligned");
+    SVI_REQUIRE(h->cfg.enable_multitalk, "svi_dit_audio_slot_windows: the model was created without enable_multitalk");
+    SVI_REQUIRE_DEVICE(h);
+    SVI_TRY(svi_dit_check_bound(h));
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    SVI_TRY(slot_ensure(h, slot, T_latent, st, "svi_dit_audio_slot_windows"));
+    AudSlot& s = h->aud_slot[slot];
     s.staged = false;
-    SVI_TRY(project_audio(h, reinterpret_cast<const bf16*>(audio_first), reinterpret_cast<const bf16*>(audio_latter), f, s.H0, s.H1, s.P3, s.AUD, st));
-    for (int l = 0; l < nl; ++l) SVI_TRY(fill_block_audio_kv(h, l, s.AUD, (int)na, s.K[l], s.VT[l], s.ld, st));
-    s.staged = true;
-    return SVI_OK;
+    SVI_TRY(svi_launch_audio_windows(emb, dtype == SVI_F32, N, SVI_AUD_ROW, start, T_latent, s.WF, T_latent > 1 ? s.WL : nullptr, st));
+    return slot_project(h, s, s.WF, s.WL, st);
 }
 
 // The three forwards of a talk step (svi_video_talk.py:455-458) in one call: cond (prompt, audio, add_condition), uncond (negative prompt, null audio,

@@ -853,3 +853,53 @@ svi_status svi_launch_cfg3_step(bf16* lat, const bf16* cond, const bf16* uncond,
     SVI_LAUNCH_CHECK();
     return SVI_OK;
 }
+
+
+// ------------------------------------------------------------------------------------------------
+// Clip audio windows of the talk stream, cut on the device (SVITalkVideoPipeline.get_audio_embedding + preprocess_audio + .to(bfloat16),
+// pipelines/svi_video_talk.py:412-446).  emb [N, R] holds one row per audio frame of the whole stream (R = 12 blocks x 768 channels in the real
+// model); a clip that starts at audio frame `start` and has T latent frames (4 (T - 1) + 1 video frames, window 5) reads, for video frame f and window
+// position w, row clamp(start + f + (w - 2), 0, N - 1):
+//   first  [5, R]         : video frame 0, positions 0..4
+//   latter [T - 1, 8, R]  : latent frame t = video frames 1 + 4t .. 4 + 4t: positions 0, 1, 2 of the first, the centre of the two middle ones,
+//                           positions 2, 3, 4 of the last
+// A clamped gather and one rounding to bf16 (round to nearest even, torch's): the result is defined bit for bit.
+// One workgroup = 256 16-byte chunks of ONE output row: the row's source index is worked out once, on the scalar unit (blockIdx only).
+// ------------------------------------------------------------------------------------------------
+template <typename SRC>
+__global__ __launch_bounds__(256) void audio_windows_kernel(const SRC* __restrict__ emb, int N, int R, long start, bf16* __restrict__ first, bf16* __restrict__ latter) {
+    const int r = blockIdx.x;                                   // output row: 0..4 = first, 5 + 8 t + j = latter[t][j]
+    long f, w;
+    bf16* out;
+    if (r < 5) { f = 0; w = r; out = first + (size_t)r * R; }
+    else {
+        const int q = r - 5, t = q >> 3, j = q & 7;
+        f = 1 + 4 * (long)t + (j < 3 ? 0 : j == 3 ? 1 : j == 4 ? 2 : 3);
+        w = j < 3 ? j : j < 5 ? 2 : j - 3;
+        out = latter + (size_t)q * R;
+    }
+    long src = start + f + w - 2;
+    src = src < 0 ? 0 : src > (long)N - 1 ? (long)N - 1 : src;
+    const int c = (blockIdx.y * 256 + threadIdx.x) * 8;
+    if (c >= R) return;                                         // R % 8 == 0: a chunk is inside the row or past it
+    const SRC* ip = emb + (size_t)src * R + c;
+    if constexpr (sizeof(SRC) == 2) st_bf16x8(out + c, ld_bf16x8(reinterpret_cast<const bf16*>(ip)));
+    else {
+        const f32x4 a = *reinterpret_cast<const f32x4*>(ip), b = *reinterpret_cast<const f32x4*>(ip + 4);
+        bf16x8 v;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { v[e] = (bf16)a[e]; v[4 + e] = (bf16)b[e]; }
+        st_bf16x8(out + c, v);
+    }
+}
+svi_status svi_launch_audio_windows(const void* emb, bool f32, int N, int R, int start, int T, bf16* first, bf16* latter, hipStream_t st) {
+    SVI_REQUIRE(emb && first && (T == 1 || latter), "audio windows: null argument");
+    SVI_REQUIRE(N >= 1 && T >= 1 && start >= 0 && R > 0 && R % 8 == 0, "audio windows: bad sizes (N %d, R %d, start %d, T %d)", N, R, start, T);
+    SVI_REQUIRE(T <= (1 << 24), "audio windows: %d latent frames", T);
+    SVI_REQUIRE((((uintptr_t)emb | (uintptr_t)first | (uintptr_t)latter) & 15) == 0, "audio windows: operands must be 16-byte aligned");
+    const dim3 grid((unsigned)(5 + 8 * (T - 1)), (unsigned)((R / 8 + 255) / 256)), block(256);
+    if (f32) hipLaunchKernelGGL(audio_windows_kernel<float>, grid, block, 0, st, reinterpret_cast<const float*>(emb), N, R, (long)start, first, latter);
+    else hipLaunchKernelGGL(audio_windows_kernel<bf16>, grid, block, 0, st, reinterpret_cast<const bf16*>(emb), N, R, (long)start, first, latter);
+    SVI_LAUNCH_CHECK();
+    return SVI_OK;
+}

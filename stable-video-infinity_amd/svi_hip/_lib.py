@@ -66,6 +66,8 @@ SYMBOLS = [
     ("svi_dit_audio_slot", _i32, [_vp, _i32, _vp, _vp, _i32, _vp]),
     ("svi_dit_forward_talk3", _i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     ("svi_dit_forward_talk3_tea", _i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    ("svi_audio_windows", _i32, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    ("svi_dit_audio_slot_windows", _i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp]),
     ("svi_cfg3_step", _i32, [_vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _vp]),
     ("svi_dit_time_mod", _i32, [_vp, _vp, _vp, _i32, _vp]),
     ("svi_dit_forward_tea", _i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),

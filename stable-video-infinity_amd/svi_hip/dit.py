@@ -391,6 +391,30 @@ class WanDiT:
                 "svi_dit_audio_slot")
         self._audio_slots[slot] = a1.shape[1] + 1
 
+    def stage_audio_windows(self, emb: torch.Tensor, start: int, T_latent: int, null_emb: Optional[torch.Tensor] = None) -> None:
+        """The clip boundary of a talk stream: both audio slots filled on the device (svi_dit_audio_slot_windows) from `emb`, the whole stream's audio
+        embedding — fp32 or bf16 [N, 12, 768], resident on the GPU — for the clip that starts at audio frame `start` (the reference's audio_start_idx) and
+        has T_latent latent frames.  Slot 0 takes emb's windows, slot 1 (the null audio) null_emb's under the same rule.  null_emb = None is the
+        reference's null audio: SVITalkVideoPipeline.__call__ builds audio_embed_tuple_null as preprocess_audio(torch.zeros_like(audio_embed)[-1:])
+        (svi_video_talk.py:550) — audio_embed is [1, frames, 5, 12, 768], so [-1:] keeps all of it: zero windows of the clip's shapes, which is what one
+        zero row gives under the clamp.  The bits are stage_audio's on host-built tuples; as there, an unchanged frame count rewrites the slots in place
+        (generation() does not move: a captured talk step stays valid)."""
+        if not self.enable_multitalk:
+            raise ValueError("stage_audio_windows on a model without enable_multitalk")
+        if null_emb is None:
+            null_emb = getattr(self, "_null_audio", None)
+            if null_emb is None or null_emb.device != emb.device:
+                null_emb = self._null_audio = torch.zeros((1, 12, 768), dtype=torch.bfloat16, device=emb.device)
+        self._refresh_if_weights_changed()
+        for slot, e in ((0, emb), (1, null_emb)):
+            if not e.is_cuda or e.dtype not in (torch.float32, torch.bfloat16) or not e.is_contiguous():
+                raise ValueError(f"stage_audio_windows: the audio embedding must be a contiguous CUDA fp32 or bf16 tensor (got {e.device}, {e.dtype})")
+            if e.dim() < 2 or e.shape[0] < 1 or e[0].numel() != 12 * 768:
+                raise ValueError(f"stage_audio_windows: the audio embedding must be [N >= 1, 12, 768], the model's audio width (got {tuple(e.shape)})")
+            L.check(L.lib().svi_dit_audio_slot_windows(self._h, slot, L.ptr(e), L.SVI_F32 if e.dtype == torch.float32 else L.SVI_BF16, e.shape[0], int(start),
+                                                       int(T_latent), L.current_stream()), "svi_dit_audio_slot_windows")
+            self._audio_slots[slot] = int(T_latent)
+
     def audio_staged(self, frames: int) -> bool:
         """Both audio slots hold projections made with the bound weights for `frames` latent frames."""
         return self._audio_slots.get(0) == frames and self._audio_slots.get(1) == frames

@@ -173,6 +173,25 @@ def cfg3_step_(latents: torch.Tensor, cond: torch.Tensor, uncond: torch.Tensor, 
     return latents
 
 
+def audio_windows(emb: torch.Tensor, start: int, T_latent: int):
+    """The talk variant's clip audio windows, cut on the device (svi_audio_windows) = get_audio_embedding + preprocess_audio + .to(bfloat16)
+    (svi_video_talk.py:412-446): emb fp32 or bf16 [N, ...] (one row per audio frame of the whole stream; [N, 12, 768] in the real model, the trailing
+    sizes' product a multiple of 8), `start` = audio_start_idx, T_latent latent frames.  Returns bf16 (first [1, 5, ...], latter [T_latent - 1, 8, ...]):
+    the row of video frame f, window position w is emb[clamp(start + f + w - 2, 0, N - 1)]."""
+    if not emb.is_cuda:
+        raise RuntimeError("emb must live on the GPU (svi_hip has no CPU path)")
+    if emb.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"emb must be fp32 or bf16, got {emb.dtype}")
+    if emb.dim() < 2 or not emb.is_contiguous():
+        raise ValueError(f"emb must be a contiguous [N, ...] tensor (got {tuple(emb.shape)})")
+    N, tail = emb.shape[0], tuple(emb.shape[1:])
+    first = torch.empty((1, 5) + tail, dtype=torch.bfloat16, device=emb.device)
+    latter = torch.empty((max(int(T_latent) - 1, 0), 8) + tail, dtype=torch.bfloat16, device=emb.device)
+    L.check(L.lib().svi_audio_windows(L.ptr(emb), L.SVI_F32 if emb.dtype == torch.float32 else L.SVI_BF16, N, emb[0].numel(), int(start), int(T_latent),
+                                      L.ptr(first), L.ptr(latter) if latter.numel() else None, L.current_stream()), "audio_windows")
+    return first, latter
+
+
 def linear_row_stats(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, eps: float = 1e-6):
     """nn.Linear whose epilogue also leaves RMSNorm's statistic of the OUTPUT rows (svi_linear_row_stats): returns (y bf16 [M, N], rs fp32 [M] =
     rsqrt(mean(y^2) + eps), row_sumsq fp32 [N/64, M]).  The cross-attention query projection of the DiT block (dit:296) runs this way."""

@@ -204,6 +204,10 @@ class DenoiseLoop:
             self.dit.context_cache(False)
         self._retire_capture_stream()                    # the stream's end also ends its capture stream and the library's buffers keyed to it
 
+    def held_graphs(self) -> list:
+        """The captured graphs the loop holds now (the plain step's, then the TeaCache ones): a stream that replays holds the same objects clip after clip."""
+        return ([self._graph["graph"]] if self._graph is not None else []) + [h["graph"] for h in self._tea_graphs.values()]
+
     def drop_graph(self) -> None:
         """Forget the captured step (a later graphed step captures again)."""
         self._graph = None
@@ -429,7 +433,9 @@ class DenoiseLoop:
         object for the conditional forward and ONE for the unconditional and the drop-text forward — consulted twice per step, in that order —, or the
         objects are given (tea_cache_posi / tea_cache_nega: svi_hip.TeaCache or the reference's class; None leaves that side without).  The one-call
         step serves them too (one forward_talk3(tea_modes) call per step, a graph per mode triple); one object given for BOTH sides keeps the eager
-        forwards (the conditional residual would be the negative one's buffer, which the one call refuses)."""
+        forwards (the conditional residual would be the negative one's buffer, which the one call refuses).
+        audio_embed_tuple = audio_embed_tuple_null = None (the one-call step only): the caller has staged both audio slots for this clip itself
+        (WanDiT.stage_audio_windows — a talk stream's clip boundary, TalkStreamLoop)."""
         from .dit import model_fn_wan_talk_video
         if tea_cache_l1_thresh is not None and tea_cache_posi is None and tea_cache_nega is None:
             from .teacache import TeaCache
@@ -443,6 +449,9 @@ class DenoiseLoop:
                 cond = dict(cond, add_condition=add_condition)
             return self._sample_talk3(latents, ctx_pos, ctx_neg, audio_embed_tuple, audio_embed_tuple_null, text_scale, audio_scale,
                                       self.scheduler.timesteps, self.scheduler.step_delta, progress_bar_cmd, cond, tea=tea)
+        if audio_embed_tuple is None or audio_embed_tuple_null is None:
+            raise ValueError("sample_multitalk: audio slots staged by the caller serve the one-call step only (a graphed single-rank loop with a guidance "
+                             "scale other than 1); this loop's eager forwards need audio_embed_tuple and audio_embed_tuple_null")
         fn = model_fn_wan_talk_video
         if self.sequence_parallel:
             self.dit.sp_group = self.sp_group
@@ -547,8 +556,13 @@ class DenoiseLoop:
             self.dit.context_cache(True)
         ts_dev = timesteps.to(device=dev, dtype=torch.float32)
         try:
-            self.dit.stage_audio(0, audio_embed_tuple)
-            self.dit.stage_audio(1, audio_embed_tuple_null)
+            if audio_embed_tuple is None and audio_embed_tuple_null is None:      # the caller staged the slots itself (WanDiT.stage_audio_windows)
+                if not self.dit.audio_staged(latents.shape[2]):
+                    raise ValueError(f"sample_multitalk without audio tuples: the DiT's audio slots are not staged for {latents.shape[2]} latent frames "
+                                     "(WanDiT.stage_audio_windows)")
+            else:
+                self.dit.stage_audio(0, audio_embed_tuple)
+                self.dit.stage_audio(1, audio_embed_tuple_null)
             if self._cond is None or self._cond.shape != latents.shape:
                 self._cond = torch.empty_like(latents)
                 self._uncond = torch.empty_like(latents)

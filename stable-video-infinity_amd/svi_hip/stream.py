@@ -127,3 +127,115 @@ class StreamLoop:
             self.trace.append(dict(clip=k, seed=seed, motion=motion, y=y, latents=lat, frames=frames))
             motion = frames[-self.num_motion_frames:]
             pieces.append(frames[:-self.num_motion_frames] if k < num_clips - 1 else frames)
+
+
+class TalkStreamLoop(StreamLoop):
+    """The clip loop of a talk stream (test_svi_talk.py:277-302 around SVITalkVideoPipeline.__call__, svi_video_talk.py:469-564), resident on the GPU.
+
+    Per clip the reference: cuts the clip's audio windows out of the whole file's wav2vec2 embedding at `audio_start_idx` (get_audio_embedding +
+    preprocess_audio, a host gather, six rearrange / concat passes and an upload), encodes the motion frames — the last `num_motion_frames` 8-bit
+    frames of the previous clip, or the input image — plus padding into y, denoises with the three-way guidance (_sample_with_multitalk), decodes,
+    converts to 8-bit frames and appends ALL of them to the video (`video_list += video`: clips are stitched whole).  Here the embedding [N, 12, 768]
+    is uploaded once; at a clip boundary both audio slots of the DiT are cut and re-projected on the device where they stand
+    (WanDiT.stage_audio_windows), so every clip after the first replays the first clip's step graph(s) on ONE DenoiseLoop(graph=True, resident=True);
+    the motion frames go through StreamLoop's 8-bit hand-off.  The audio encoder is outside: it runs once per audio file, its output is this
+    loop's input.  Clips chain, so there is no clip-per-rank mode; under a CFG pair the talk step's three forwards have no home and it is refused.
+    With sequence_parallel the loop keeps DenoiseLoop's eager shard forwards (the windows are cut on the device all the same, ops.audio_windows)."""
+
+    def __init__(self, dit, vae, clip_encoder: Optional[Callable[[torch.Tensor], torch.Tensor]] = None, num_motion_frames: int = 1,
+                 num_frames: int = 81, num_inference_steps: int = 50, cfg_scale: Optional[dict] = None, sigma_shift: float = 5.0,
+                 ref_pad_cfg: bool = False, ref_pad_num: int = 0, tea_cache_l1_thresh: Optional[float] = None, tea_cache_model_id: str = "",
+                 tiled: bool = False, tile_size=(30, 52), tile_stride=(15, 26), vae_split=None, vae_group=None, cfg_pair=None, sp_group=None,
+                 sequence_parallel: bool = False, vae_encode_split=None):
+        """cfg_scale = dict(audio=, text=) (test_svi_talk.py:287-289; default audio 4, text 5).  tea_cache_l1_thresh / tea_cache_model_id: TeaCache with
+        fresh objects per clip, as SVITalkVideoPipeline.__call__ makes them (svi_video_talk.py:541-542).  Everything else as StreamLoop."""
+        if cfg_pair is not None:
+            raise ValueError("TalkStreamLoop: the talk step has three guidance forwards whose branches differ in their audio; a CFG-pair rank serves two "
+                             "(use sequence_parallel, or one rank)")
+        if not getattr(dit, "enable_multitalk", False):
+            raise ValueError("TalkStreamLoop needs a DiT with enable_multitalk")
+        if num_frames % 4 != 1:
+            raise ValueError(f"num_frames must be 4 k + 1 (got {num_frames}; the reference rounds it up before it cuts the audio, svi_video_talk.py:499-501)")
+        cfg_scale = dict(cfg_scale or dict(audio=4.0, text=5.0))
+        if set(cfg_scale) != {"audio", "text"}:
+            raise ValueError(f"cfg_scale must be dict(audio=, text=) (got {cfg_scale!r})")
+        super().__init__(dit, vae, clip_encoder=clip_encoder, num_motion_frames=num_motion_frames, num_frames=num_frames,
+                         num_inference_steps=num_inference_steps, cfg_scale=cfg_scale, sigma_shift=sigma_shift, ref_pad_cfg=ref_pad_cfg,
+                         ref_pad_num=ref_pad_num, tiled=tiled, tile_size=tile_size, tile_stride=tile_stride, vae_split=vae_split, vae_group=vae_group,
+                         sp_group=sp_group, sequence_parallel=sequence_parallel, vae_encode_split=vae_encode_split)
+        if not sequence_parallel:
+            self.loop = DenoiseLoop(dit, graph=True, resident=True)
+        self.tea = dict(tea_cache_l1_thresh=tea_cache_l1_thresh, tea_cache_model_id=tea_cache_model_id)
+
+    def audio_start(self, k: int) -> int:
+        """Clip k's audio_start_idx: k clips' worth of frames, minus the motion frames every clip after the first re-renders (test_svi_talk.py:278-280,
+        with the clip's own frame count in the place of the script's 81)."""
+        return k * self.num_frames - (self.num_motion_frames if k > 0 else 0)
+
+    @torch.no_grad()
+    def run(self, input_frames_u8: torch.Tensor, ref_frame_u8: torch.Tensor, prompt: tuple, audio_emb: torch.Tensor, num_clips: int, seed=0,
+            clip_feature: Optional[torch.Tensor] = None, null_emb: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """input_frames_u8 [n, H, W, 3] (the input image, n = 1), ref_frame_u8 [H, W, 3] (`random_ref_frame`, fixed for the stream), prompt =
+        (context_pos, context_neg) embeddings, audio_emb fp32 or bf16 [N, 12, 768]: the audio encoder's output for the whole stream (a stream that
+        outlasts it keeps reading its last row: the reference's clamp).  seed: one int for every clip (the reference's call) or one per clip.
+        null_emb: WanDiT.stage_audio_windows's.  Returns the stitched 8-bit video [num_clips * num_frames, H, W, 3] on the GPU: every clip whole."""
+        seeds = [int(seed)] * num_clips if isinstance(seed, int) else [int(s) for s in seed]
+        if len(seeds) != num_clips:
+            raise ValueError(f"{len(seeds)} seeds for {num_clips} clips")
+        if audio_emb.dim() != 3 or tuple(audio_emb.shape[1:]) != (12, 768) or audio_emb.shape[0] < 1:
+            raise ValueError(f"audio_emb must be [N >= 1, 12, 768] (got {tuple(audio_emb.shape)})")
+        emb = audio_emb.to("cuda")
+        emb = (emb if emb.dtype in (torch.float32, torch.bfloat16) else emb.float()).contiguous()
+        if null_emb is not None:
+            null_emb = null_emb.to("cuda").contiguous()
+        motion = input_frames_u8.to("cuda")
+        ref = u8_to_video(ref_frame_u8.to("cuda")[None])[0]
+        H, W = motion.shape[1:3]
+        tlat = (self.num_frames - 1) // 4 + 1
+        ctx_pos, ctx_neg = prompt
+        scales = dict(text_scale=float(self.cfg_scale["text"]), audio_scale=float(self.cfg_scale["audio"]))
+        slots = self.loop.graph and (scales["text_scale"] != 1.0 or scales["audio_scale"] != 1.0)      # sample_multitalk's one-call step reads the slots
+        pieces = []
+        self.trace = []
+        cache_was_on = self.loop.dit._ctx_cache_on
+        try:
+            for k in range(num_clips):
+                first = u8_to_video(motion)
+                y = image_condition(self.vae, first, ref, self.num_frames, self.ref_pad_cfg, self.ref_pad_num, **self.vae_encode_split)
+                if self.clip_encoder is None:
+                    cf = clip_feature
+                elif hasattr(self.clip_encoder, "encode_image"):
+                    cf = self.clip_encoder.encode_image([first[:1]]).to(torch.bfloat16)
+                else:
+                    cf = self.clip_encoder(first[:1])
+                start = self.audio_start(k)
+                if slots:
+                    self.loop.dit.stage_audio_windows(emb, start, tlat, null_emb)
+                    aud = aud0 = None
+                else:
+                    aud, aud0 = self._tuples(emb, start, tlat), self._tuples(null_emb, start, tlat)
+                lat = generate_noise((1, 16, tlat, H // 8, W // 8), seed=seeds[k], device="cpu", dtype=torch.float32).to("cuda", torch.bfloat16)
+                cond = dict(y=y)
+                if cf is not None:
+                    cond["clip_feature"] = cf
+                lat = self.loop.sample_multitalk(lat, ctx_pos, ctx_neg, aud, aud0, num_inference_steps=self.steps, sigma_shift=self.sigma_shift,
+                                                 **scales, **self.tea, **cond)
+                video = self.vae.decode(lat.float(), device="cuda", **self.tiler, **self.vae_split)[0]
+                frames = video_to_u8(video)
+                self.trace.append(dict(clip=k, seed=seeds[k], audio_start=start, motion=motion, y=y, latents=lat, frames=frames,
+                                       captures=self.loop.captures, graphs=self.loop.held_graphs(), generation=self.loop.dit.generation()))
+                motion = frames[-self.num_motion_frames:]
+                pieces.append(frames)                   # `video_list += video` in both branches of test_svi_talk.py:304-308: every clip whole
+        finally:
+            if not cache_was_on:
+                self.loop.close()
+        return torch.cat(pieces, dim=0)
+
+    @staticmethod
+    def _tuples(emb: Optional[torch.Tensor], start: int, tlat: int):
+        """audio_embed_tuple for the eager forwards, cut on the device; None: the reference's null audio (zeros, svi_video_talk.py:550)."""
+        from .ops import audio_windows
+        if emb is None:
+            emb = torch.zeros((1, 12, 768), dtype=torch.bfloat16, device="cuda")
+        first, latter = audio_windows(emb, start, tlat)
+        return first[None], latter[None]

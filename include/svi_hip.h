@@ -602,6 +602,34 @@ svi_status svi_pose_bind_weight(svi_pose* h, const char* name, const void* dev_p
 svi_status svi_pose_check_bound(svi_pose* h);
 svi_status svi_pose_tokens(svi_pose* h, int32_t F, int32_t H, int32_t W, int32_t* f, int32_t* hh, int32_t* ww);
 svi_status svi_pose_forward(svi_pose* h, const float* pose, void* out, int32_t F, int32_t H, int32_t W, svi_stream stream);
+/* The clip boundary of a dance STREAM (additive in v13): clip k's pose window cut on the device out of the whole pose video.
+ *
+ * svi_pose_window: pose u8 [N, h, w, 3] — the pose video as the video reader hands it over, at its source resolution — is read for clip k of a
+ * stream whose clips have F frames and hand m motion frames from clip to clip; out f32 [3, F, H, W], values 0..255, is svi_pose_forward's input.
+ * This is what the reference's script does between two clips on the host (test_svi_dance.py:215-227, 281-288 around
+ * utils/image_process.py:134-170 resize_and_pad_to_target), with F where the script hard-codes 81:
+ *   Frame.  Window frame i of clip k: while k > 0 and i < m, it is frame F - m + i of clip k - 1 (the carried motion poses; i and k step back until
+ *     the frame is one a clip read for itself).  Then g = i when k == 0, else g = (F - 1) + (k - 1)(F - m) + (i - m): the script's read cursor starts
+ *     clip 1 at F - 1, so frame F - 1 is read twice (its quirk), and runs on over the clips.  The source frame is g mod N: the wrap of the cursor, and
+ *     also the repeat-padding of a video shorter than a clip (the padded length is a multiple of N).  The script's `stride` is read and never
+ *     applied; nor is it here.
+ *   Size.  s = min(H / h, W / w) in double; nh = (int)(h * s), nw = (int)(w * s), truncated (so nh can be H - 1 where h * (H / h) lands just under
+ *     H); pad_top = (H - nh) / 2, pad_left = (W - nw) / 2, integer division: the odd pixel goes to the bottom / right.
+ *   Row and column.  Output row y in [pad_top, pad_top + nh) reads source row min((int)floorf((y - pad_top) * rs), h - 1), rs = (float)h / (float)nh
+ *     in fp32 — F.interpolate(mode='nearest') with the output size given.  Columns alike with w, nw, pad_left.  Everything outside is 0.
+ * One launch; no host table, no allocation, no copy: the scalars are the kernel's arguments.  A lane owns four neighbouring columns of one output row
+ * in all three channels (the three bytes of a source pixel are read together) and writes one 16-byte store per channel when W % 4 == 0 and out is
+ * 16-byte aligned (4-byte stores otherwise); the padding is written as zeros by the same launch.  Source offsets are 64-bit (N * h * w * 3 passes
+ * 2^31 for an ordinary video); F <= 65535 and H * W < 2^31.
+ *
+ * svi_pose_window_plan: the same rule on the host, no device touched: frame_src[F] (source frame of every window frame), row_src[H] and col_src[W]
+ * (source row / column, -1 where the output is padding).  The kernel and the plan call the same inline functions.
+ *
+ * Both refuse, with a message and before any launch: a NULL pointer, N < 1, F < 2, m < 1 or m >= F, k < 0, h or w < 1, H or W < 16, nh or nw < 1. */
+svi_status svi_pose_window(const uint8_t* pose, float* out, int32_t N, int32_t h, int32_t w, int32_t H, int32_t W, int32_t F, int32_t m, int32_t k,
+                           svi_stream stream);
+svi_status svi_pose_window_plan(int32_t N, int32_t h, int32_t w, int32_t H, int32_t W, int32_t F, int32_t m, int32_t k, int32_t* frame_src,
+                                int32_t* row_src, int32_t* col_src);
 
 /* ------------------------------------------------------------------ prompt-side encoders ------- */
 /* WanTextEncoder (models/wan_video_text_encoder.py:209-256): the umT5 encoder behind WanPrompter.encode_prompt

@@ -124,6 +124,8 @@ SYMBOLS = [
     ("svi_pose_check_bound", _i32, [_vp]),
     ("svi_pose_tokens", _i32, [_vp, _i32, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)]),
     ("svi_pose_forward", _i32, [_vp, _vp, _vp, _i32, _i32, _i32, _vp]),
+    ("svi_pose_window", _i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    ("svi_pose_window_plan", _i32, [_i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)]),
     ("svi_t5_create", _i32, [C.POINTER(T5Config), C.POINTER(_vp)]),
     ("svi_t5_destroy", _i32, [_vp]),
     ("svi_t5_bind_weight", _i32, [_vp, C.c_char_p, _vp, _i32, C.POINTER(_i64), _i32]),
@@ -239,6 +241,14 @@ def vae_tile_order(ord_T: int, ord_Lf: int, ord_G: int) -> list:
     out = (_i64 * (ord_T * ord_Lf))()
     check(lib().svi_vae_tile_order(ord_T, ord_Lf, ord_G, out), "svi_vae_tile_order")
     return list(out)
+
+
+def pose_window_plan(N: int, h: int, w: int, H: int, W: int, F: int, m: int, k: int) -> dict:
+    """The rule of svi_pose_window on the host (see include/svi_hip.h): for clip k of a dance stream, the source frame of every window frame, and the
+    source row / column of every output row / column (-1: padding)."""
+    frame, row, col = (_i32 * max(F, 1))(), (_i32 * max(H, 1))(), (_i32 * max(W, 1))()
+    check(lib().svi_pose_window_plan(N, h, w, H, W, F, m, k, frame, row, col), "svi_pose_window_plan")
+    return {"frame_src": list(frame), "row_src": list(row), "col_src": list(col)}
 
 
 def vae_split_plan(hh: int, ww: int, parts_h: int, parts_w: int, part: int) -> dict:

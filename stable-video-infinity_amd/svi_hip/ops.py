@@ -192,6 +192,29 @@ def audio_windows(emb: torch.Tensor, start: int, T_latent: int):
     return first, latter
 
 
+def pose_window(pose_u8: torch.Tensor, k: int, num_frames: int, num_motion_frames: int, height: int, width: int,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The dance variant's clip pose window, cut on the device (svi_pose_window): pose_u8 uint8 [N, h, w, 3], the whole pose video as the video reader
+    hands it over, -> fp32 [3, num_frames, height, width], values 0..255: the `humanpose_data` of clip k, as the reference's script builds it between two
+    clips (test_svi_dance.py:215-227, 281-288: the last num_motion_frames poses carried over, the rest read on from a cursor that wraps; every frame
+    resized with nearest-neighbour, padded to the centre).  The rule is stated in include/svi_hip.h.  Written into `out` when given."""
+    if not pose_u8.is_cuda:
+        raise RuntimeError("pose_u8 must live on the GPU (svi_hip has no CPU path)")
+    if pose_u8.dtype != torch.uint8 or pose_u8.dim() != 4 or pose_u8.shape[0] < 1 or pose_u8.shape[3] != 3:
+        raise ValueError(f"pose_u8 must be uint8 [N >= 1, h, w, 3] (got {pose_u8.dtype}, {tuple(pose_u8.shape)})")
+    if not pose_u8.is_contiguous():
+        raise ValueError("pose_u8 must be contiguous")
+    N, h, w, _ = pose_u8.shape
+    shape = (3, int(num_frames), int(height), int(width))
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=pose_u8.device)
+    elif not out.is_cuda or out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous CUDA fp32 tensor {shape} (got {out.dtype}, {tuple(out.shape)})")
+    L.check(L.lib().svi_pose_window(L.ptr(pose_u8), L.ptr(out), N, h, w, shape[2], shape[3], shape[1], int(num_motion_frames), int(k),
+                                    L.current_stream()), "pose_window")
+    return out
+
+
 def linear_row_stats(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, eps: float = 1e-6):
     """nn.Linear whose epilogue also leaves RMSNorm's statistic of the OUTPUT rows (svi_linear_row_stats): returns (y bf16 [M, N], rs fp32 [M] =
     rsqrt(mean(y^2) + eps), row_sumsq fp32 [N/64, M]).  The cross-attention query projection of the DiT block (dit:296) runs this way."""

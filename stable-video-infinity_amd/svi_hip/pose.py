@@ -4,6 +4,8 @@
     PoseEmbedder.from_module(seq)           <- an existing reference nn.Sequential (fp32 parameters borrowed)
     embedder(humanpose_data)                <- :527-530: cat(first frame x3, pose) / 255 -> dwpose_embedding -> bf16 ->
                                                rearrange 'b c f h w -> b (f h w) c'   = the `add_condition` of model_fn_wan_video
+    embedder.window(pose_u8, k, F, m, H, W) <- the same for clip k of a stream, the window cut on the device out of the whole 8-bit pose video
+                                               (test_svi_dance.py:215-227, 281-288; svi_pose_window)
 
 The seven Conv3d + SiLU layers run on the exact-fp32 MFMA convolution of the VAE (csrc/svi_vae.hip); the last one stores the bf16
 token rows directly.  In the sampler the condition goes to the CONDITIONAL forward only (the unconditional one gets None unless
@@ -26,6 +28,7 @@ class PoseEmbedder:
         L.check(L.lib().svi_pose_create(hidden, dim, C.byref(h)), "svi_pose_create")
         self._h = h
         self._params: Dict[str, torch.Tensor] = {}
+        self._windows: Dict[tuple, torch.Tensor] = {}      # window(): the fp32 pose window per (frames, height, width, device)
 
     @classmethod
     def from_state_dict(cls, state_dict: Dict[str, torch.Tensor], device="cuda") -> "PoseEmbedder":
@@ -63,6 +66,20 @@ class PoseEmbedder:
         out = torch.empty((1, f * h * w, self.dim), dtype=torch.bfloat16, device=x.device)
         L.check(L.lib().svi_pose_forward(self._h, L.ptr(x), L.ptr(out), F, H, W, L.current_stream()), "svi_pose_forward")
         return out
+
+    def window(self, pose_u8: torch.Tensor, k: int, num_frames: int, num_motion_frames: int, height: int, width: int) -> torch.Tensor:
+        """Clip k's add_condition straight from the resident pose video: pose_u8 uint8 [N, h, w, 3] on the GPU -> ops.pose_window (the rolling window,
+        nearest resize and centre pad of test_svi_dance.py:215-227, 281-288, cut on the device) -> this embedder; the bits of __call__ on the window built
+        on the host.  The fp32 window [3, num_frames, height, width] is kept per shape, so a clip boundary allocates only its result."""
+        from .ops import pose_window
+        key = (int(num_frames), int(height), int(width), pose_u8.device)
+        buf = self._windows.get(key)
+        if buf is None:
+            buf = pose_window(pose_u8, k, num_frames, num_motion_frames, height, width)      # refused arguments leave no buffer behind
+            self._windows[key] = buf
+        else:
+            pose_window(pose_u8, k, num_frames, num_motion_frames, height, width, out=buf)
+        return self(buf)
 
     def __del__(self):
         try:

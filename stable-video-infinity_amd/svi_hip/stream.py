@@ -103,17 +103,20 @@ class StreamLoop:
                 self.loop.close()      # the resident loop keeps the context cache on from clip to clip; hand the model back as it came
         return torch.cat(pieces, dim=0)
 
+    def _clip_feature(self, first: torch.Tensor, clip_feature: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+        """The CLIP feature of a clip's first motion frame, or the caller's when the loop has no encoder."""
+        if self.clip_encoder is None:
+            return clip_feature
+        if hasattr(self.clip_encoder, "encode_image"):                            # svi_hip.WanImageEncoder: clip_context of svi_video.py:317, :355
+            return self.clip_encoder.encode_image([first[:1]]).to(torch.bfloat16)
+        return self.clip_encoder(first[:1])
+
     def _clips(self, clips, num_clips, motion, ref, prompts, prompt_repeat_times, use_first_prompt_only, clip_feature, pieces, H, W, tlat) -> None:
         from .parallel import clip_prompt_index, clip_seed
         for k in clips:
             first = u8_to_video(motion)                                          # preprocess_image of every motion frame
             y = image_condition(self.vae, first, ref, self.num_frames, self.ref_pad_cfg, self.ref_pad_num, **self.vae_encode_split)
-            if self.clip_encoder is None:
-                cf = clip_feature
-            elif hasattr(self.clip_encoder, "encode_image"):                      # svi_hip.WanImageEncoder: clip_context of svi_video.py:317, :355
-                cf = self.clip_encoder.encode_image([first[:1]]).to(torch.bfloat16)
-            else:
-                cf = self.clip_encoder(first[:1])
+            cf = self._clip_feature(first, clip_feature)
             ctx_pos, ctx_neg = prompts[clip_prompt_index(k, len(prompts), prompt_repeat_times, use_first_prompt_only)]
             seed = clip_seed(k, self.seed_times)
             lat = generate_noise((1, 16, tlat, H // 8, W // 8), seed=seed, device="cpu", dtype=torch.float32).to("cuda", torch.bfloat16)
@@ -202,12 +205,7 @@ class TalkStreamLoop(StreamLoop):
             for k in range(num_clips):
                 first = u8_to_video(motion)
                 y = image_condition(self.vae, first, ref, self.num_frames, self.ref_pad_cfg, self.ref_pad_num, **self.vae_encode_split)
-                if self.clip_encoder is None:
-                    cf = clip_feature
-                elif hasattr(self.clip_encoder, "encode_image"):
-                    cf = self.clip_encoder.encode_image([first[:1]]).to(torch.bfloat16)
-                else:
-                    cf = self.clip_encoder(first[:1])
+                cf = self._clip_feature(first, clip_feature)
                 start = self.audio_start(k)
                 if slots:
                     self.loop.dit.stage_audio_windows(emb, start, tlat, null_emb)
@@ -239,3 +237,93 @@ class TalkStreamLoop(StreamLoop):
             emb = torch.zeros((1, 12, 768), dtype=torch.bfloat16, device="cuda")
         first, latter = audio_windows(emb, start, tlat)
         return first[None], latter[None]
+
+
+class DanceStreamLoop(StreamLoop):
+    """The clip loop of a dance stream (test_svi_dance.py:238-288 around SVIDanceVideoPipeline.__call__, svi_video_dance.py:447-546), resident on the GPU.
+
+    Between two clips the reference's script builds the next pose window on the host — the last `num_motion_frames` poses of the previous window, the
+    rest read on from the whole pose video at a cursor that wraps; every frame resized with nearest-neighbour and padded to the centre; converted to
+    float and uploaded (3 F H W fp32 values) — and the pipeline embeds it (dwpose_embedding, :527-530) into the `add_condition` of both guidance
+    forwards (`cond_wo_pose`) or of the conditional one alone.  Here the pose video is uploaded once, as the 8-bit frames [N, h, w, 3] the video reader
+    hands over; a clip boundary is one window launch with scalar arguments (PoseEmbedder.window) and the embedder, and every clip after the first
+    replays the first clip's step graph on ONE DenoiseLoop(resident=True), which copies the condition into the tensor it owns.  The motion frames go
+    through StreamLoop's 8-bit hand-off, the video is stitched by StreamLoop's rule (every clip but the last loses its final motion frames, :262-267).
+    The dance pipeline's encode_images_adaptive is the plain one, line for line (svi_video_dance.py:314-387 / svi_video.py:291-364): image_condition."""
+
+    def __init__(self, dit, vae, pose_embedder, clip_encoder: Optional[Callable[[torch.Tensor], torch.Tensor]] = None, num_motion_frames: int = 1,
+                 num_frames: int = 81, num_inference_steps: int = 50, cfg_scale: Optional[dict] = None, sigma_shift: float = 5.0,
+                 cond_wo_pose: bool = True, remove_pose: bool = False, ref_pad_cfg: bool = False, ref_pad_num: int = 0,
+                 tea_cache_l1_thresh: Optional[float] = None, tea_cache_model_id: str = "", tiled: bool = False, tile_size=(30, 52),
+                 tile_stride=(15, 26), vae_split=None, vae_group=None, cfg_pair=None, sp_group=None, sequence_parallel: bool = False,
+                 vae_encode_split=None):
+        """pose_embedder: an svi_hip.PoseEmbedder of the DiT's width.  cfg_scale = dict(audio=, text=) as the script passes it (test_svi_dance.py:248-250);
+        the sampler reads 'text' only (svi_video_dance.py:421-433).  cond_wo_pose: the pose condition also on the unconditional forward — True is what the
+        script passes (:259).  remove_pose: the script's --remove_pose, no pose condition at all (:252).  tea_cache_l1_thresh / tea_cache_model_id: TeaCache
+        with fresh objects per clip, as SVIDanceVideoPipeline.__call__ makes them (svi_video_dance.py:519-520).  Everything else as StreamLoop."""
+        if num_frames % 4 != 1:
+            raise ValueError(f"num_frames must be 4 k + 1 (got {num_frames}; the pose window and the latents are cut for the same frame count)")
+        if num_motion_frames < 1 or num_motion_frames >= num_frames:
+            raise ValueError(f"num_motion_frames must be in 1 .. num_frames - 1 = {num_frames - 1} (got {num_motion_frames}): the pose window carries "
+                             "them over and reads on")
+        cfg_scale = dict(cfg_scale or dict(audio=4.0, text=5.0))
+        if "text" not in cfg_scale:
+            raise ValueError(f"cfg_scale must be a dict with 'text' (got {cfg_scale!r})")
+        if pose_embedder.dim != dit.dim:
+            raise ValueError(f"the pose embedder's dim {pose_embedder.dim} is not the DiT's dim {dit.dim}")
+        super().__init__(dit, vae, clip_encoder=clip_encoder, num_motion_frames=num_motion_frames, num_frames=num_frames,
+                         num_inference_steps=num_inference_steps, cfg_scale=cfg_scale, sigma_shift=sigma_shift, ref_pad_cfg=ref_pad_cfg,
+                         ref_pad_num=ref_pad_num, tiled=tiled, tile_size=tile_size, tile_stride=tile_stride, vae_split=vae_split, vae_group=vae_group,
+                         cfg_pair=cfg_pair, sp_group=sp_group, sequence_parallel=sequence_parallel, vae_encode_split=vae_encode_split)
+        self.pose_embedder, self.cond_wo_pose, self.remove_pose = pose_embedder, bool(cond_wo_pose), bool(remove_pose)
+        self.tea = dict(tea_cache_l1_thresh=tea_cache_l1_thresh, tea_cache_model_id=tea_cache_model_id)
+
+    @torch.no_grad()
+    def run(self, input_frames_u8: torch.Tensor, ref_frame_u8: torch.Tensor, prompt: tuple, pose_u8: torch.Tensor, num_clips: int, seed=0,
+            clip_feature: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """input_frames_u8 [n, H, W, 3] (the reference image at the clip size, n = 1), ref_frame_u8 [H, W, 3] (`random_ref_frame`, fixed for the stream),
+        prompt = (context_pos, context_neg) embeddings, pose_u8 uint8 [N, h, w, 3]: the whole pose video at its source resolution (a stream that
+        outlasts it wraps around; one shorter than a clip repeats).  seed: one int for every clip or one per clip (the script passes None: random).
+        Returns the stitched 8-bit video on the GPU: every clip but the last loses its final `num_motion_frames` frames."""
+        seeds = [int(seed)] * num_clips if isinstance(seed, int) else [int(s) for s in seed]
+        if len(seeds) != num_clips:
+            raise ValueError(f"{len(seeds)} seeds for {num_clips} clips")
+        if pose_u8.dtype != torch.uint8 or pose_u8.dim() != 4 or pose_u8.shape[0] < 1 or pose_u8.shape[3] != 3:
+            raise ValueError(f"pose_u8 must be uint8 [N >= 1, h, w, 3] (got {pose_u8.dtype}, {tuple(pose_u8.shape)})")
+        motion = input_frames_u8.to("cuda")
+        H, W = motion.shape[1:3]
+        tlat = (self.num_frames - 1) // 4 + 1
+        pt, ph, pw = self.loop.dit.patch_size
+        grid, pose_grid = (tlat // pt, H // 8 // ph, W // 8 // pw), self.pose_embedder.tokens(self.num_frames, H, W)
+        if pose_grid != grid:
+            raise ValueError(f"the pose embedder's token grid {pose_grid} for {self.num_frames} frames of {H} x {W} is not the DiT's {grid} for the clip's latents")
+        pose = pose_u8.to("cuda").contiguous()                   # once per stream
+        ref = u8_to_video(ref_frame_u8.to("cuda")[None])[0]
+        ctx_pos, ctx_neg = prompt
+        pieces = []
+        self.trace = []
+        cache_was_on = self.loop.dit._ctx_cache_on
+        try:
+            for k in range(num_clips):
+                first = u8_to_video(motion)
+                y = image_condition(self.vae, first, ref, self.num_frames, self.ref_pad_cfg, self.ref_pad_num, **self.vae_encode_split)
+                cond = dict(y=y)
+                cf = self._clip_feature(first, clip_feature)
+                if cf is not None:
+                    cond["clip_feature"] = cf
+                if not self.remove_pose:
+                    cond["add_condition"] = self.pose_embedder.window(pose, k, self.num_frames, self.num_motion_frames, H, W)
+                lat = generate_noise((1, 16, tlat, H // 8, W // 8), seed=seeds[k], device="cpu", dtype=torch.float32).to("cuda", torch.bfloat16)
+                lat = self.loop.sample(lat, ctx_pos, ctx_neg, num_inference_steps=self.steps, cfg_scale=float(self.cfg_scale["text"]),
+                                       sigma_shift=self.sigma_shift, cond_wo_pose=self.cond_wo_pose, **self.tea, **cond)
+                video = self.vae.decode(lat.float(), device="cuda", **self.tiler, **self.vae_split)[0]
+                frames = video_to_u8(video)
+                self.trace.append(dict(clip=k, seed=seeds[k], pose_window=None if self.remove_pose else k, motion=motion, y=y,
+                                       add_condition=cond.get("add_condition"), latents=lat, frames=frames, captures=self.loop.captures,
+                                       graphs=self.loop.held_graphs()))
+                motion = frames[-self.num_motion_frames:]
+                pieces.append(frames[:-self.num_motion_frames] if k < num_clips - 1 else frames)
+        finally:
+            if not cache_was_on:
+                self.loop.close()
+        return torch.cat(pieces, dim=0)

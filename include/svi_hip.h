@@ -46,7 +46,8 @@ typedef enum {
     SVI_ERR_OOM = 5
 } svi_status;
 
-typedef enum { SVI_BF16 = 0, SVI_F32 = 1, SVI_F16 = 2 /* LoRA operands only (svi_lora_merge_e4m3) */ } svi_dtype;
+typedef enum { SVI_BF16 = 0, SVI_F32 = 1, SVI_F16 = 2 /* LoRA operands only (svi_lora_merge_e4m3) */,
+               SVI_E4M3 = 3 /* OCP e4m3fn bytes: the DiT blocks' Linear weights bound FP8-resident (svi_dit_bind_weight) */ } svi_dtype;
 
 typedef void* svi_stream;
 typedef struct svi_dit svi_dit;
@@ -98,8 +99,11 @@ int32_t svi_switch_state(const char* name);
 svi_status svi_dit_create(const svi_dit_config* cfg, svi_dit** out);
 svi_status svi_dit_destroy(svi_dit* h);
 /* name = reference state-dict key, e.g. "blocks.0.self_attn.q.weight" (models/wan_video_dit.py
- * module tree).  dtype must be SVI_BF16 (the pipelines run the DiT in bf16, pipelines/svi_video.py:259).
- * shape is checked against the config. */
+ * module tree).  dtype must be SVI_BF16 (the pipelines run the DiT in bf16, pipelines/svi_video.py:259) — except the 2-D Linear weights inside
+ * blocks.* (self_attn.{q,k,v,o}, cross_attn.{q,k,v,o,k_img,v_img}, ffn.{0,2}, audio_cross_attn.{q_linear,kv_linear,proj}), which may also be bound as
+ * SVI_E4M3: the stored bytes of the reference's FP8 mode themselves, [out, in] contiguous.  Their GEMMs then widen the bytes to bf16 on the way into the
+ * matrix pipe (svi_gemm_bf16_w8) — the same bits as binding the bf16 cast, one byte per parameter resident instead of two more.  A handle may mix both;
+ * norms, biases, modulation, embedders and the head stay bf16.  shape is checked against the config. */
 svi_status svi_dit_bind_weight(svi_dit* h, const char* name, const void* dev_ptr, svi_dtype dtype,
                                const int64_t* shape, int32_t rank);
 /* Returns SVI_OK when every parameter the config requires has been bound; otherwise
@@ -369,6 +373,9 @@ svi_status svi_attention_last_flagged(svi_stream stream, int32_t* flagged_out, i
  * svi_attention_plan: out4 = {kernel (1 = short key axes, 2 = long-sequence kernel), work items run whole, pieces per remaining item, workgroups}:
  * the items of a partly filled last round are cut along the key axis (csrc/svi_attention.hip flash_splits). */
 svi_status svi_gemm_plan(int32_t M, int32_t N, int32_t K, int32_t epilogue, int32_t skinny, int32_t compute_units, int32_t* kernel_out);
+/* svi_gemm_w8_plan: the kernel svi_gemm_bf16_w8 takes for the same problem — svi_gemm_plan's answer where that kernel has an e4m3-weight form (0 and 128);
+ * the LDS-DMA fed tiles (192 / 259 / 260) have none and map to 128. */
+svi_status svi_gemm_w8_plan(int32_t M, int32_t N, int32_t K, int32_t epilogue, int32_t skinny, int32_t compute_units, int32_t* kernel_out);
 svi_status svi_attention_plan(int32_t s_q, int32_t s_kv, int32_t heads, int32_t compute_units, int32_t* out4);
 /* ABI v11 — the VAE's plane-fed residual-block convolution (3x3x3 over Cin -> Cout, stride 1, causal, 'same'; input [frames][Ho][Wo][Cin]):
  * svi_vae_conv_plan: out8 = {kernel (0 = the layer does not take the producer's fp16 planes, 1 = conv_dma2h_kernel<1> (Cout <= 32), 3 = conv_dma2h_kernel<3>,
@@ -424,6 +431,22 @@ svi_status svi_gemm_bf16_pair(const void* A, int32_t lda, const void* W, int32_t
                               int32_t epilogue, const float* gate, const void* res, int32_t ldres,
                               const void* W2, const void* bias2, int32_t n_split, int32_t sel_m, int32_t sel_n,
                               svi_stream stream);
+/* The weight-streaming skinny kernel (plan id 0: M <= 128 rows against a large weight, K % 128 == 0, epilogue SVI_EPI_BIAS or SVI_EPI_BIAS_GATE_RES, ldc % 4 == 0
+ * — the text encoder's projections) as an operator seam.  w8 = 0: W bf16 [N, ldw]; w8 != 0: W stored as e4m3 bytes [N, ldw bytes], widened in front of the
+ * matrix instruction — bit-identical to w8 = 0 on the widened copy.  Refused when the shape does not take that kernel. */
+svi_status svi_gemm_bf16_skinny(const void* A, int32_t lda, const void* W, int32_t ldw, void* C, int32_t ldc, int32_t M, int32_t N, int32_t K,
+                                const void* bias, int32_t epilogue, const float* gate, const void* res, int32_t ldres, int32_t w8, svi_stream stream);
+/* FP8-resident weights: svi_gemm_bf16_pair with W (and W2) stored as OCP e4m3fn BYTES, [N, ldw] with ldw in bytes, a multiple of 16 (W / W2 16-byte aligned):
+ *     C = epi(A[M, K] bf16 · widen(W8[N, K])^T)
+ * The bytes are widened to bf16 (exactly: all 256 codes, subnormals m * 2^-9, signed zeros, S.1111.111 = NaN — svi_fp8_e4m3_to_bf16's mapping) between the
+ * global load and the matrix instruction, so per output element the sums and their order are those of svi_gemm_bf16_pair on the widened copy run on the
+ * kernel svi_gemm_w8_plan names: bit-identical, at half the weight bytes from HBM.  Every epilogue, W2 / n_split, sel_m / sel_n and bias_along_m as there.
+ * Refused with a message, before any launch: a NULL A / W / C, an ldw that is not a multiple of 16. */
+svi_status svi_gemm_bf16_w8(const void* A, int32_t lda, const void* W8, int32_t ldw, void* C, int32_t ldc,
+                            int32_t M, int32_t N, int32_t K, const void* bias, int32_t bias_along_m,
+                            int32_t epilogue, const float* gate, const void* res, int32_t ldres,
+                            const void* W2_8, const void* bias2, int32_t n_split, int32_t sel_m, int32_t sel_n,
+                            svi_stream stream);
 
 /* ---- MX-fp8 (opt-in; north_star "bf16/fp8 MFMA").  The reference computes in bf16 and only STORES weights as float8_e4m3fn
  * (test_svi.py:337, vram_management/layers.py:65-71): what follows is arithmetic it never performs — own tolerance, own bench line.
@@ -470,7 +493,8 @@ svi_status svi_cfg3_step(void* latents, const void* cond, const void* uncond, co
 
 /* FP8 weight storage: the reference's `torch_dtype=torch.float8_e4m3fn` mode (test_svi.py:337) keeps parameters as OCP e4m3fn and
  * casts them to bf16 in front of every use (vram_management/layers.py:65-71, cast_to).  The cast is exact, so it is done once:
- * out bf16 [n] = bf16(in e4m3fn [n]); bind the result with svi_dit_bind_weight.  (svi_hip.WanDiT.bind does this for fp8 tensors.) */
+ * out bf16 [n] = bf16(in e4m3fn [n]); bind the result with svi_dit_bind_weight.  (svi_hip.WanDiT.bind does this for fp8 tensors; with fp8_resident=True it
+ * binds the blocks' Linear weights as SVI_E4M3 instead and casts only the small rest.) */
 svi_status svi_fp8_e4m3_to_bf16(const void* in, void* out, int64_t n, svi_stream stream);
 
 /* The cast back: out e4m3fn [n] = cast(in [n]), in fp32 (SVI_F32) or bf16 (SVI_BF16, widened exactly), with the semantics of torch's

@@ -502,6 +502,37 @@ extern "C" svi_status svi_gemm_bf16_pair(const void* A, int32_t lda, const void*
     return svi_launch_gemm(g, reinterpret_cast<hipStream_t>(stream));
 }
 
+// svi_gemm_bf16_pair with W / W2 stored as e4m3 bytes (ldw in bytes): what a DiT bound with FP8-resident weights launches for its projections
+extern "C" svi_status svi_gemm_bf16_w8(const void* A, int32_t lda, const void* W, int32_t ldw, void* C, int32_t ldc, int32_t M,
+                                       int32_t N, int32_t K, const void* bias, int32_t bias_along_m, int32_t epilogue,
+                                       const float* gate, const void* res, int32_t ldres, const void* W2, const void* bias2,
+                                       int32_t n_split, int32_t sel_m, int32_t sel_n, svi_stream stream) {
+    SVI_REQUIRE(A && W && C, "svi_gemm_bf16_w8: null argument");
+    SVI_REQUIRE(ldw % 16 == 0, "svi_gemm_bf16_w8: ldw = %d bytes must be a multiple of 16", ldw);
+    SviGemmArgs g{};
+    g.A = reinterpret_cast<const bf16*>(A); g.lda = lda; g.W = reinterpret_cast<const bf16*>(W); g.ldw = ldw;
+    g.C = reinterpret_cast<bf16*>(C); g.ldc = ldc; g.M = M; g.N = N; g.K = K;
+    g.bias = reinterpret_cast<const bf16*>(bias); g.bias_along_m = bias_along_m; g.epi = epilogue; g.gate = gate;
+    g.res = reinterpret_cast<const bf16*>(res); g.ldres = ldres;
+    if (W2) { g.W2 = reinterpret_cast<const bf16*>(W2); g.bias2 = reinterpret_cast<const bf16*>(bias2); g.n_split = n_split; }
+    g.sel_m = sel_m; g.sel_n = sel_n;
+    return svi_launch_gemm_e8(g, 1, reinterpret_cast<hipStream_t>(stream));
+}
+
+// The weight-streaming skinny launch (M <= 128 rows against a large weight: what the text encoder's projections run) as an operator seam, with W bf16
+// (w8 = 0) or stored as e4m3 bytes (w8 != 0, ldw in bytes): the two are bit-identical on the widened copy (tests/test_gpu_gemm_w8.py).
+extern "C" svi_status svi_gemm_bf16_skinny(const void* A, int32_t lda, const void* W, int32_t ldw, void* C, int32_t ldc, int32_t M, int32_t N, int32_t K,
+                                           const void* bias, int32_t epilogue, const float* gate, const void* res, int32_t ldres, int32_t w8, svi_stream stream) {
+    SVI_REQUIRE(A && W && C, "svi_gemm_bf16_skinny: null argument");
+    SviGemmArgs g{};
+    g.A = reinterpret_cast<const bf16*>(A); g.lda = lda; g.W = reinterpret_cast<const bf16*>(W); g.ldw = ldw;
+    g.C = reinterpret_cast<bf16*>(C); g.ldc = ldc; g.M = M; g.N = N; g.K = K;
+    g.bias = reinterpret_cast<const bf16*>(bias); g.epi = epilogue; g.gate = gate; g.res = reinterpret_cast<const bf16*>(res); g.ldres = ldres;
+    g.skinny = 1;
+    SVI_REQUIRE(svi_gemm_choose(g, 256) == 0, "svi_gemm_bf16_skinny: M = %d, K = %d, epilogue %d do not take the skinny kernel (M <= 128, K %% 128 == 0, bias or gate + residual)", M, K, epilogue);
+    return w8 ? svi_launch_gemm_e8(g, 1, reinterpret_cast<hipStream_t>(stream)) : svi_launch_gemm(g, reinterpret_cast<hipStream_t>(stream));
+}
+
 // The cross-attention query path as the DiT block runs it, in two seams (CrossAttention.forward, models/wan_video_dit.py:266-303: q = norm_q(self.q(x)), then
 // attention against the prompt's K / V): the projection that also leaves the RMSNorm statistic, and the short-key attention that normalises q as it reads it.
 extern "C" svi_status svi_linear_row_stats(const void* A, int32_t lda, const void* W, int32_t ldw, void* C, int32_t ldc, int32_t M, int32_t N, int32_t K,
@@ -545,6 +576,13 @@ extern "C" svi_status svi_gemm_plan(int32_t M, int32_t N, int32_t K, int32_t epi
     SviGemmArgs g{};
     g.M = M; g.N = N; g.K = K; g.lda = K; g.ldw = K; g.ldc = (N + 7) / 8 * 8; g.epi = epilogue; g.skinny = skinny;
     *kernel_out = svi_gemm_choose(g, compute_units);
+    return SVI_OK;
+}
+extern "C" svi_status svi_gemm_w8_plan(int32_t M, int32_t N, int32_t K, int32_t epilogue, int32_t skinny, int32_t compute_units, int32_t* kernel_out) {
+    SVI_REQUIRE(kernel_out && M > 0 && N > 0 && K > 0 && compute_units > 0, "svi_gemm_w8_plan: bad argument");
+    SviGemmArgs g{};
+    g.M = M; g.N = N; g.K = K; g.lda = K; g.ldw = K; g.ldc = (N + 7) / 8 * 8; g.epi = epilogue; g.skinny = skinny;
+    *kernel_out = svi_gemm_choose_e8(g, compute_units, 1);
     return SVI_OK;
 }
 extern "C" svi_status svi_attention_plan(int32_t s_q, int32_t s_kv, int32_t heads, int32_t compute_units, int32_t* out4) {

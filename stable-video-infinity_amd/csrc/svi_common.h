@@ -228,6 +228,11 @@ struct SviGemmArgs {
 unsigned long long svi_stream_buffer_generation();       // moves whenever a per-stream library buffer is freed (svi_api.hip)
 svi_status svi_launch_gemm(const SviGemmArgs& g, hipStream_t st);
 int svi_gemm_choose(const SviGemmArgs& g, int compute_units);          // which kernel svi_launch_gemm takes (pure; see svi_gemm.hip)
+// FP8-resident weights: the same GEMM with ONE operand stored as OCP e4m3 bytes and widened (exactly) on its way into the matrix pipe — e8 = 1: g.W (and g.W2)
+// [N, ldw bytes]; e8 = 2: g.A [M, lda bytes] (the transposed value projection: the stored weight is the A operand).  The leading dimension of the e4m3 operand
+// is in bytes, a multiple of 16.  Per element the bits of svi_launch_gemm on the widened copy, run on the kernel svi_gemm_choose_e8 names (0 or 128).
+svi_status svi_launch_gemm_e8(const SviGemmArgs& g, int e8, hipStream_t st);
+int svi_gemm_choose_e8(const SviGemmArgs& g, int compute_units, int e8);
 // how svi_launch_flash splits a launch into work items (pure; see svi_attention.hip): items [0, whole) run whole, the rest in `pieces` workgroups each
 struct SviFlashSplit { int whole, pieces, qblocks, heads; };
 SviFlashSplit svi_flash_plan(int Lq, int Lk, int heads, int cus, int* kernel_out);

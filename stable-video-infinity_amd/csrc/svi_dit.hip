@@ -23,7 +23,9 @@
 
 namespace {
 
-struct Lin { const bf16* w = nullptr; const bf16* b = nullptr; };
+// e4m3: w points at the STORED OCP e4m3 bytes of the weight (FP8-resident binding, svi_dit_bind_weight with SVI_E4M3) — the GEMM widens them on their way
+// into the matrix pipe (lin_gemm); the bias is bf16 either way
+struct Lin { const bf16* w = nullptr; const bf16* b = nullptr; bool e4m3 = false; };
 struct AttnW {
     Lin q, k, v, o;
     const bf16* norm_q = nullptr;
@@ -44,7 +46,7 @@ struct BlockW {
     const bf16* normx_w = nullptr;
     const bf16* normx_b = nullptr;
 };
-struct Slot { const bf16** ptr; std::vector<int64_t> shape; };
+struct Slot { const bf16** ptr; std::vector<int64_t> shape; bool* e4m3 = nullptr; };      // e4m3: where the slot records an e4m3 binding (null: bf16 only)
 
 struct Workspace {
     int L = 0, Lc = 0;              // the problem the pointers below are laid out for
@@ -207,8 +209,10 @@ __global__ void unpatchify_kernel(const bf16* __restrict__ ho, bf16* __restrict_
 static void add_slot(svi_dit* h, const std::string& name, const bf16** p, std::vector<int64_t> shape) {
     h->slots[name] = Slot{p, std::move(shape)};
 }
-static void add_lin(svi_dit* h, const std::string& name, Lin* l, int64_t o, int64_t i) {
+// may8: the weight may also be bound as stored e4m3 bytes (the Linear weights inside blocks.*: everything that is large)
+static void add_lin(svi_dit* h, const std::string& name, Lin* l, int64_t o, int64_t i, bool may8 = false) {
     add_slot(h, name + ".weight", &l->w, {o, i});
+    if (may8) h->slots[name + ".weight"].e4m3 = &l->e4m3;
     add_slot(h, name + ".bias", &l->b, {o});
 }
 
@@ -240,26 +244,26 @@ extern "C" svi_status svi_dit_create(const svi_dit_config* c, svi_dit** out) {
         for (int a = 0; a < 2; ++a) {
             AttnW& w = a ? b.ca : b.sa;
             const std::string ap = p + (a ? "cross_attn." : "self_attn.");
-            add_lin(h, ap + "q", &w.q, D, D);
-            add_lin(h, ap + "k", &w.k, D, D);
-            add_lin(h, ap + "v", &w.v, D, D);
-            add_lin(h, ap + "o", &w.o, D, D);
+            add_lin(h, ap + "q", &w.q, D, D, true);
+            add_lin(h, ap + "k", &w.k, D, D, true);
+            add_lin(h, ap + "v", &w.v, D, D, true);
+            add_lin(h, ap + "o", &w.o, D, D, true);
             add_slot(h, ap + "norm_q.weight", &w.norm_q, {D});
             add_slot(h, ap + "norm_k.weight", &w.norm_k, {D});
             if (a && c->has_image_input) {
-                add_lin(h, ap + "k_img", &w.k_img, D, D);
-                add_lin(h, ap + "v_img", &w.v_img, D, D);
+                add_lin(h, ap + "k_img", &w.k_img, D, D, true);
+                add_lin(h, ap + "v_img", &w.v_img, D, D, true);
                 add_slot(h, ap + "norm_k_img.weight", &w.norm_k_img, {D});
             }
         }
         add_slot(h, p + "norm3.weight", &b.norm3_w, {D});
         add_slot(h, p + "norm3.bias", &b.norm3_b, {D});
-        add_lin(h, p + "ffn.0", &b.ffn0, F, D);
-        add_lin(h, p + "ffn.2", &b.ffn2, D, F);
+        add_lin(h, p + "ffn.0", &b.ffn0, F, D, true);
+        add_lin(h, p + "ffn.2", &b.ffn2, D, F, true);
         if (c->enable_multitalk) {          // dit:338-351: encoder_hidden_states_dim = 768, qkv_bias, no qk norm
-            add_lin(h, p + "audio_cross_attn.q_linear", &b.aud_q, D, D);
-            add_lin(h, p + "audio_cross_attn.kv_linear", &b.aud_kv, 2 * D, 768);
-            add_lin(h, p + "audio_cross_attn.proj", &b.aud_proj, D, D);
+            add_lin(h, p + "audio_cross_attn.q_linear", &b.aud_q, D, D, true);
+            add_lin(h, p + "audio_cross_attn.kv_linear", &b.aud_kv, 2 * D, 768, true);
+            add_lin(h, p + "audio_cross_attn.proj", &b.aud_proj, D, D, true);
             add_slot(h, p + "norm_x.weight", &b.normx_w, {D});
             add_slot(h, p + "norm_x.bias", &b.normx_b, {D});
         }
@@ -305,13 +309,16 @@ extern "C" svi_status svi_dit_bind_weight(svi_dit* h, const char* name, const vo
     SVI_REQUIRE(h && name && dev_ptr && shape, "svi_dit_bind_weight: null argument");
     auto it = h->slots.find(name);
     if (it == h->slots.end()) { svi_set_error("unknown DiT parameter '%s'", name); return SVI_ERR_INVALID; }
-    SVI_REQUIRE(dtype == SVI_BF16, "DiT parameter '%s' must be bf16", name);
+    SVI_REQUIRE(dtype == SVI_BF16 || (dtype == SVI_E4M3 && it->second.e4m3), "DiT parameter '%s' must be bf16%s", name, it->second.e4m3 ? " or e4m3" : "");
     const std::vector<int64_t>& want = it->second.shape;
     bool ok = (int)want.size() == rank;
     for (int i = 0; ok && i < rank; ++i) ok = want[i] == shape[i];
     if (!ok) { svi_set_error("shape mismatch for '%s'", name); return SVI_ERR_INVALID; }
     SVI_REQUIRE(((uintptr_t)dev_ptr % 16) == 0, "parameter '%s' is not 16-byte aligned", name);
+    // (an e4m3 row is its GEMM's leading dimension in bytes: svi_launch_gemm_e8 wants a multiple of 16 — refused here, not at the first launch)
+    SVI_REQUIRE(dtype != SVI_E4M3 || shape[rank - 1] % 16 == 0, "parameter '%s' as e4m3: the inner dimension %lld must be a multiple of 16", name, (long long)shape[rank - 1]);
     *it->second.ptr = reinterpret_cast<const bf16*>(dev_ptr);
+    if (it->second.e4m3) *it->second.e4m3 = dtype == SVI_E4M3;
     for (auto& e : h->ctx_entries) e.filled = false;      // cached projections were made with the old weights
     for (auto& s : h->aud_slot) s.staged = false;         // and so were the audio slots'
     ++h->generation;
@@ -547,13 +554,19 @@ static svi_status ensure_rope(svi_dit* h, int f, int hh, int ww) {
 // ------------------------------------------------------------------------------------------------
 // nb > 1: the M rows are nb samples stacked one under the other; the kernel is chosen as for ONE sample (M / nb rows), so a stacked
 // launch computes every row with the kernel — and the bits — a per-sample launch would.
+// THE place a projection's GEMM is launched from: a weight bound as bf16 takes the bf16 kernels, one bound as stored e4m3 bytes (FP8-resident) the forms that
+// widen it on the way in — the W operand, or the A operand of the transposed value projection.  Every path (plain, pair, stacked, shard, talk3, TeaCache,
+// context-cache fill) comes through here, and a handle may mix the two.  ld of a [N, K] weight is K elements = K bytes when e4m3.
+static svi_status lin_gemm(const SviGemmArgs& g, const Lin& l, bool weight_is_a, hipStream_t st) {
+    return l.e4m3 ? svi_launch_gemm_e8(g, weight_is_a ? 2 : 1, st) : svi_launch_gemm(g, st);
+}
 static svi_status linear(const bf16* A, int lda, const Lin& l, bf16* C, int ldc, int M, int N, int K, int epi,
                          hipStream_t st, const float* gate = nullptr, const bf16* res = nullptr, int ldres = 0, int nb = 1) {
     SviGemmArgs g{};
     g.A = A; g.lda = lda; g.W = l.w; g.ldw = K; g.C = C; g.ldc = ldc; g.M = M; g.N = N; g.K = K;
     g.bias = l.b; g.epi = epi; g.gate = gate; g.res = res; g.ldres = ldres;
     g.sel_m = nb > 1 ? M / nb : 0;
-    return svi_launch_gemm(g, st);
+    return lin_gemm(g, l, false, st);
 }
 // V^T[D, n_tok] = Wv · X^T + bv (bias along rows): same GEMM with the operands swapped.
 static svi_status linear_transposed(const bf16* Xin, int ldx, const Lin& l, bf16* CT, int ldct, int n_tok, int N, int K,
@@ -562,7 +575,7 @@ static svi_status linear_transposed(const bf16* Xin, int ldx, const Lin& l, bf16
     g.A = l.w; g.lda = K; g.W = Xin; g.ldw = ldx; g.C = CT; g.ldc = ldct; g.M = N; g.N = n_tok; g.K = K;
     g.bias = l.b; g.bias_along_m = 1; g.epi = SVI_EPI_BIAS;
     g.sel_n = nb > 1 ? n_tok / nb : 0;
-    return svi_launch_gemm(g, st);
+    return lin_gemm(g, l, true, st);
 }
 
 // Opt-in MX-fp8 projections (svi_dit_proj_mx8): y = epi(quantised(A) · W8^T) for one of the block's square projections.  `A` [R, D] bf16 is quantised into the
@@ -612,7 +625,7 @@ static svi_status block_qkv(svi_dit* h, int layer, const bf16* X, const float* m
         g.A = reinterpret_cast<const bf16*>(b.proj_8[2]); g.lda = D; g.W = reinterpret_cast<const bf16*>(w.Q8); g.ldw = D; g.C = VT; g.ldc = ldvt; g.M = D; g.N = L; g.K = D;
         g.bias = b.sa.v.b; g.bias_along_m = 1; g.epi = SVI_EPI_BIAS;
         SVI_TRY(svi_launch_gemm_mx8_wscaled(g, w.S8, w.sc_rows, st));
-    } else if (!svi_switches().qk_fused) {
+    } else if (!svi_switches().qk_fused || b.sa.q.e4m3 != b.sa.k.e4m3) {          // (one of the pair stored as e4m3, the other bf16: two launches, the same bits)
         { SviProfScope _p(PROF_GEMM_QKV, st); SVI_TRY(linear(w.Hb, D, b.sa.q, QK, 2 * D, L, D, D, SVI_EPI_BIAS, st, nullptr, nullptr, 0, nb)); }
         { SviProfScope _p(PROF_GEMM_QKV, st); SVI_TRY(linear(w.Hb, D, b.sa.k, QK + D, 2 * D, L, D, D, SVI_EPI_BIAS, st, nullptr, nullptr, 0, nb)); }
     } else {
@@ -622,7 +635,7 @@ static svi_status block_qkv(svi_dit* h, int layer, const bf16* X, const float* m
       g.bias = b.sa.q.b; g.epi = SVI_EPI_BIAS;
       g.W2 = b.sa.k.w; g.bias2 = b.sa.k.b; g.n_split = D;
       g.sel_m = nb > 1 ? L / nb : 0; g.sel_n = D;
-      SVI_TRY(svi_launch_gemm(g, st)); }
+      SVI_TRY(lin_gemm(g, b.sa.q, false, st)); }
     if (part == 0 && !(proj_mx8_on(h) && !scatter)) { SviProfScope _p(PROF_GEMM_QKV, st); SVI_TRY(linear_transposed(w.Hb, D, b.sa.v, VT, ldvt, L, D, D, st, nb)); }
     // q and k in one launch (grid.y = operand): q additionally carries softmax_scale * log2(e) into its single final rounding
     if (q8) { SviProfScope _p(PROF_RMS_ROPE, st); return svi_launch_rmsnorm_rope2_q8(QK, 2 * D, L, D, b.sa.norm_q, b.sa.norm_k, c.eps, &rope, SVI_QK_SCALE_LOG2E, 1.0f, st, *q8); }
@@ -710,7 +723,7 @@ static svi_status run_block_rest_n(svi_dit* h, int layer, bf16* X, const bf16* c
         g.bias = b.ca.q.b; g.epi = SVI_EPI_BIAS;
         g.sel_m = nb > 1 ? R / nb : 0;
         if (fused) { g.rowss = w.RSS; g.ldss = w.ldss; }
-        SVI_TRY(svi_launch_gemm(g, st));
+        SVI_TRY(lin_gemm(g, b.ca.q, false, st));
     }
     if (fused) { SviProfScope _p(PROF_FLASH_CROSS, st); SVI_TRY(svi_launch_row_rs(w.RSS, D / 64, w.ldss, R, D, c.eps, w.RS, st)); }      // (timed with the attention it feeds)
     else { SviProfScope _p(PROF_RMS_ROPE, st); SVI_TRY(svi_launch_rmsnorm_rope(w.QK, 2 * D, R, D, b.ca.norm_q, c.eps, nullptr, SVI_QK_SCALE_LOG2E, st)); }
@@ -830,7 +843,8 @@ static svi_status stage_audio(svi_dit* h, int f, hipStream_t st) {
 static svi_status fill_block_audio_kv(svi_dit* h, int layer, const bf16* AUD, int na, bf16* K, bf16* VT, int ld, hipStream_t st) {
     const BlockW& b = h->blocks[layer];
     const int D = h->cfg.dim;
-    const Lin lk{b.aud_kv.w, b.aud_kv.b}, lv{b.aud_kv.w + (size_t)D * SVI_AUD_DIM, b.aud_kv.b + D};
+    const size_t v_off = (size_t)D * SVI_AUD_DIM * (b.aud_kv.e4m3 ? 1 : 2);          // bytes to the V half of the [2 D, 768] weight
+    const Lin lk{b.aud_kv.w, b.aud_kv.b, b.aud_kv.e4m3}, lv{reinterpret_cast<const bf16*>(reinterpret_cast<const char*>(b.aud_kv.w) + v_off), b.aud_kv.b + D, b.aud_kv.e4m3};
     SVI_TRY(linear(AUD, SVI_AUD_DIM, lk, K, D, na, D, SVI_AUD_DIM, SVI_EPI_BIAS, st));
     return linear_transposed(AUD, SVI_AUD_DIM, lv, VT, ld, na, D, SVI_AUD_DIM, st);
 }

@@ -21,6 +21,9 @@
 //
 // Workgroup ids are remapped so that the 8 XCDs each own a contiguous band of tiles (per-XCD L2 keeps
 // the shared A row-panel hot; cdna_hip_programming.md T1, bijective form).
+//
+// FP8-resident weights (svi_launch_gemm_e8): the 128^2 tile and the skinny kernel also exist with one operand stored as OCP e4m3 bytes, widened exactly to
+// bf16 on its way in (gemm_e8_nt_kernel, gemm_skinny_w8_kernel) — the bits of the bf16 kernels on the widened copy at half that operand's bytes from HBM.
 #include <stdlib.h>
 #include <string.h>
 #include <type_traits>
@@ -51,6 +54,19 @@ __device__ __forceinline__ void gemm_rowss_store(const SviGemmArgs& g, const bf1
     ss += __shfl_xor(ss, 4);
     if ((lane_chunk & 7) == 0) g.rowss[(size_t)(n >> 6) * g.ldss + m] = ss;
 }
+
+// Eight stored OCP e4m3 bytes -> eight bf16, exact for all 256 codes (the mapping of svi_fp8_e4m3_to_bf16: subnormals m * 2^-9, signed zeros kept, S.1111.111 =
+// NaN, no infinity): v_cvt_scalef32_pk_bf16_fp8 with the scale 1.0 widens two bytes per instruction — four VALU instructions per staged chunk, against the
+// five integer operations per ELEMENT a sign / exponent / mantissa re-pack with its subnormal and NaN cases costs.
+__device__ __forceinline__ u32x4 e4m3x8_to_bf16x8(u32x2 b) {
+    return u32x4{__builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(b[0], 1.0f, false)),
+                 __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(b[0], 1.0f, true)),
+                 __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(b[1], 1.0f, false)),
+                 __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(b[1], 1.0f, true))};
+}
+// a staged 8-element chunk as the LDS image / the MFMA wants it: bf16 as it is, e4m3 widened
+__device__ __forceinline__ u32x4 gemm_chunk_bf16(u32x4 v) { return v; }
+__device__ __forceinline__ u32x4 gemm_chunk_bf16(u32x2 v) { return e4m3x8_to_bf16x8(v); }
 
 // PF = K tiles of global loads in flight (a register ring of PF slots, the K loop unrolled by PF so that every slot is a fixed register set and the compiler
 // counts vmcnt itself).  PF = 1 is the loop as rounds 1-6 had it (two workgroups per CU share a SIMD's issue slots).  PF = 4 serves launches of at most one
@@ -260,6 +276,219 @@ __global__ __launch_bounds__(NT, (PF == 1 && NT == 256) ? 2 : 1) void gemm_bf16_
         }
     }
 }
+
+// The same tile with ONE operand stored as OCP e4m3 bytes (FP8-resident weights; svi_launch_gemm_e8) — E8 = 1: W [N, ldw bytes]; E8 = 2: A [M, lda bytes], the
+// transposed value projection, where the stored weight is the A operand.  The bytes are widened to bf16 between their global load and their LDS write: the
+// register ring holds 8 bytes per chunk instead of 16; the LDS image, the fragment reads, the MFMAs, their k order and the epilogue are gemm_bf16_nt_kernel's
+// line for line — the same bits as that kernel on the widened copy (tests/test_gpu_gemm_w8.py).  A kernel of its own and not a mode of the template above:
+// routing both through one body moved the bf16 instantiations' register allocation (171 -> 174, 158 -> 162 VGPRs), and those are the measured product kernels.
+template <int PF, int NT, int E8>
+__global__ __launch_bounds__(NT, (PF == 1 && NT == 256) ? 2 : 1) void gemm_e8_nt_kernel(SviGemmArgs g, int tiles_m, int tiles_n) {
+    static_assert(E8 == 1 || E8 == 2, "which operand is e4m3");
+    constexpr bool A8 = E8 == 2, W8 = E8 == 1;
+    using AT = std::conditional_t<A8, unsigned char, bf16>;    // a stored element (an e4m3 leading dimension counts bytes = elements)
+    using WT = std::conditional_t<W8, unsigned char, bf16>;
+    using RA = std::conditional_t<A8, u32x2, u32x4>;           // one staged 8-element chunk as it comes from memory
+    using RW = std::conditional_t<W8, u32x2, u32x4>;
+    constexpr int WNC = NT / 128;           // wave columns (2 or 4)
+    constexpr int NBW = 8 / WNC;            // 16-column blocks per wave (4 or 2)
+    constexpr int LJ = 1024 / NT;           // 16-byte chunks of an operand tile per thread (4 or 2)
+    constexpr int LR = NT / 8;              // tile rows one pass of the staging assignment covers (32 or 64)
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int wm = wave / WNC, wn = wave % WNC;
+    const int l15 = lane & 15, g4 = lane >> 4;
+
+    // XCD-aware, bijective remap of the linear workgroup id
+    const int nwg = tiles_m * tiles_n;
+    const int orig = blockIdx.x;
+    const int xcd = orig & 7, q = nwg >> 3, rr = nwg & 7;
+    const int swz = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (orig >> 3);
+    const int tile_m = swz / tiles_n, tile_n = swz - tile_m * tiles_n;
+    const int m0 = tile_m * BM, n0 = tile_n * BN;
+    if (g.W2 && n0 >= g.n_split) {                          // q | k side by side: this tile's columns belong to the second matrix
+        g.W = reinterpret_cast<const bf16*>(reinterpret_cast<const WT*>(g.W2) - (size_t)g.n_split * g.ldw);
+        g.bias = g.bias2 ? g.bias2 - g.n_split : nullptr;
+    }
+
+    // global -> register staging assignment: 1024 8-element chunks per operand tile, LJ per thread
+    const int ld_row = tid >> 3;            // + LR*j
+    const int ld_chunk = tid & 7;
+    const AT* a_ptr[LJ];
+    const WT* w_ptr[LJ];
+    bool a_ok[LJ], w_ok[LJ];
+#pragma unroll
+    for (int j = 0; j < LJ; ++j) {
+        const int r = ld_row + LR * j;
+        a_ok[j] = (m0 + r) < g.M;
+        w_ok[j] = (n0 + r) < g.N;
+        a_ptr[j] = reinterpret_cast<const AT*>(g.A) + (size_t)(a_ok[j] ? (m0 + r) : 0) * g.lda + ld_chunk * 8;
+        w_ptr[j] = reinterpret_cast<const WT*>(g.W) + (size_t)(w_ok[j] ? (n0 + r) : n0) * g.ldw + ld_chunk * 8;          // (n0, not 0: row 0 of a base moved back for W2 lies before W2)
+    }
+    const int nk = (g.K + BK - 1) / BK;
+    RA ra[PF][LJ];
+    RW rw[PF][LJ];
+    const RA zero_a = RA(0u);          // (e4m3 0x00 widens to +0)
+    const RW zero_w = RW(0u);
+
+    auto load_tile = [&](RA (&xa)[LJ], RW (&xw)[LJ], int kt) {
+        if constexpr (PF > 1) {          // K % 64 == 0 (the launcher's condition): no k tail, and a row past the edge reads row 0 (its results are never stored) —
+#pragma unroll                           // no predicate, no branch around a load: the compiler's vmcnt arithmetic keeps PF - 1 tiles in flight
+            for (int j = 0; j < LJ; ++j) {
+                xa[j] = *reinterpret_cast<const RA*>(a_ptr[j] + kt * BK);
+                xw[j] = *reinterpret_cast<const RW*>(w_ptr[j] + kt * BK);
+            }
+            return;
+        }
+        const int kbase = kt * BK + ld_chunk * 8;
+        const bool kin = kbase < g.K;          // K % 8 == 0: a chunk is entirely inside or outside
+#pragma unroll
+        for (int j = 0; j < LJ; ++j) {
+            xa[j] = (a_ok[j] && kin) ? *reinterpret_cast<const RA*>(a_ptr[j] + kt * BK) : zero_a;
+            xw[j] = (w_ok[j] && kin) ? *reinterpret_cast<const RW*>(w_ptr[j] + kt * BK) : zero_w;
+        }
+    };
+    auto store_tile = [&](const RA (&xa)[LJ], const RW (&xw)[LJ], int buf) {
+        char* As = smem + buf * 2 * STAGE_BYTES;
+        char* Ws = As + STAGE_BYTES;
+#pragma unroll
+        for (int j = 0; j < LJ; ++j) {
+            const int off = lds_tile_off(ld_row + LR * j, ld_chunk);
+            *reinterpret_cast<u32x4*>(As + off) = gemm_chunk_bf16(xa[j]);
+            *reinterpret_cast<u32x4*>(Ws + off) = gemm_chunk_bf16(xw[j]);
+        }
+    };
+
+    f32x4 acc[NBW][4];                      // [nb][mb]: 16 x 16 blocks, lane l holds n = 4 (l >> 4) + e of row m = l & 15
+#pragma unroll
+    for (int i = 0; i < NBW; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) acc[i][j][r] = 0.f;
+
+#pragma unroll
+    for (int s = 0; s < PF; ++s) load_tile(ra[s], rw[s], s);          // (PF > 1: the launcher guarantees nk >= PF; PF = 1: nk >= 1)
+    store_tile(ra[0], rw[0], 0);
+    __syncthreads();
+
+    // one K tile: slot s of the ring held tile kt (in LDS since the step before; tile 0: the prologue) and takes tile kt + PF; tile kt + 1 moves to LDS behind the MFMAs
+    auto kstep = [&](RA (&la)[LJ], RW (&lw)[LJ], const RA (&sa)[LJ], const RW (&sw_)[LJ], int kt, bool ld, bool st) {
+        const int cur = kt & 1;
+        if (ld) load_tile(la, lw, kt + PF);
+        const char* As = smem + cur * 2 * STAGE_BYTES;
+        const char* Ws = As + STAGE_BYTES;
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk) {          // two k-steps of 32: lane group g4 holds k = 8 g4 .. 8 g4 + 7 of the step
+            bf16x8 xa[4], wb[NBW];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) xa[i] = *reinterpret_cast<const bf16x8*>(As + lds_tile_off(wm * 64 + i * 16 + l15, 4 * kk + g4));
+#pragma unroll
+            for (int i = 0; i < NBW; ++i) wb[i] = *reinterpret_cast<const bf16x8*>(Ws + lds_tile_off(wn * (16 * NBW) + i * 16 + l15, 4 * kk + g4));
+#pragma unroll
+            for (int nb = 0; nb < NBW; ++nb)
+#pragma unroll
+                for (int mb = 0; mb < 4; ++mb)
+                    acc[nb][mb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wb[nb], xa[mb], acc[nb][mb], 0, 0, 0);
+        }
+        if (st) store_tile(sa, sw_, cur ^ 1);
+        __syncthreads();
+    };
+    // steady state: every step loads and stores — no branch between a load and the wait that counts it, so PF - 1 tiles stay in flight (a conditional
+    // load makes the compiler's vmcnt arithmetic assume the shorter path: vmcnt(0) every step, which is what the PF = 1 loop pays by construction)
+    int kt0 = 0;
+    for (; kt0 + 2 * PF <= nk; kt0 += PF) {
+#pragma unroll
+        for (int s = 0; s < PF; ++s) kstep(ra[s], rw[s], ra[(s + 1) % PF], rw[(s + 1) % PF], kt0 + s, true, true);
+    }
+    for (; kt0 < nk; kt0 += PF) {                 // the last PF .. 2 PF - 1 tiles
+#pragma unroll
+        for (int s = 0; s < PF; ++s) {
+            const int kt = kt0 + s;
+            if (kt < nk) kstep(ra[s], rw[s], ra[(s + 1) % PF], rw[(s + 1) % PF], kt, kt + PF < nk, kt + 1 < nk);
+        }
+    }
+
+    // ---- epilogue part 1: y = bf16(acc + bias) -> LDS [128 m][CS_LD] bf16 --------------------------
+    // acc[nb][mb][e] is C[m = m0 + wm*64 + mb*16 + l15][n = n0 + wn*(16 NBW) + nb*16 + 4*g4 + e]
+    bf16* Cs = reinterpret_cast<bf16*>(smem);
+#pragma unroll
+    for (int nb = 0; nb < NBW; ++nb) {
+        const int nl = wn * (16 * NBW) + nb * 16 + 4 * g4;
+        float bn[4] = {0.f, 0.f, 0.f, 0.f};
+        if (g.bias && !g.bias_along_m) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) bn[e] = (n0 + nl + e < g.N) ? (float)g.bias[n0 + nl + e] : 0.f;
+        }
+#pragma unroll
+        for (int mb = 0; mb < 4; ++mb) {
+            const int ml = wm * 64 + mb * 16 + l15;
+            float bm = 0.f;
+            if (g.bias && g.bias_along_m) bm = (m0 + ml < g.M) ? (float)g.bias[m0 + ml] : 0.f;
+            bf16x4 pk;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) pk[e] = (bf16)(acc[nb][mb][e] + ((g.bias && g.bias_along_m) ? bm : bn[e]));
+            *reinterpret_cast<bf16x4*>(Cs + ml * CS_LD + nl) = pk;
+        }
+    }
+    __syncthreads();
+
+    // ---- epilogue part 2: row-contiguous read-back, activation / gate / residual, coalesced store ----
+#pragma unroll
+    for (int it = 0; it < 2048 / NT; ++it) {
+        const int id = tid + NT * it;
+        const int ml = id >> 4, cc = id & 15;
+        const int m = m0 + ml, n = n0 + cc * 8;
+        if (m >= g.M || n >= g.N) continue;
+        bf16x8 yv = *reinterpret_cast<const bf16x8*>(Cs + ml * CS_LD + cc * 8);
+        float y[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) y[e] = (float)yv[e];
+        const bool full = (n + 8 <= g.N);
+        if (g.epi == SVI_EPI_BIAS_GELU_TANH) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) y[e] = gelu_tanh_f(y[e]);
+        } else if (g.epi == SVI_EPI_BIAS_GELU_ERF) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) y[e] = gelu_erf_f(y[e]);
+        } else if (g.epi == SVI_EPI_BIAS_SILU) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) y[e] = silu_f(y[e]);
+        } else if (g.epi == SVI_EPI_BIAS_RELU) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) y[e] = fmaxf(y[e], 0.f);
+        } else if (g.epi == SVI_EPI_BIAS_GATE_RES) {
+            const bf16* rp = g.res + (size_t)m * g.ldres + n;
+            float rv[8];
+            if (full) {
+                bf16x8 t = ld_bf16x8(rp);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) rv[e] = (float)t[e];
+            } else {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) rv[e] = (n + e < g.N) ? (float)rp[e] : 0.f;
+            }
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                float t = y[e];
+                if (g.gate) t = rbf(((n + e < g.N) ? g.gate[n + e] : 0.f) * t);
+                y[e] = rv[e] + t;
+            }
+        }
+        bf16* cp = g.C + (size_t)m * g.ldc + n;
+        if (full) {
+            bf16x8 o;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) o[e] = (bf16)y[e];
+            st_bf16x8(cp, o);
+            if (g.rowss) gemm_rowss_store(g, o, m, n, cc);          // (N % 64 == 0: a group's 8 lanes are all here)
+        } else {
+            for (int e = 0; e < 8 && n + e < g.N; ++e) cp[e] = (bf16)y[e];
+        }
+    }
+}
+
 
 
 // =================================================================================================
@@ -911,6 +1140,73 @@ __global__ __launch_bounds__(64 * NW) void gemm_skinny_kernel(SviGemmArgs g) {
     }
 }
 
+// gemm_skinny_kernel with W stored as e4m3 bytes [N, ldw bytes] (FP8-resident weights; a kernel of its own for the reason gemm_e8_nt_kernel is): a lane's fragment is 8 bytes from memory, widened to bf16 in front of its MFMA —
+// half the bytes of the stream this kernel exists for, the same MFMAs in the same order: the bits of the bf16 form on the widened copy.
+template <int MB, int NW, int UN>
+__global__ __launch_bounds__(64 * NW) void gemm_skinny_w8_kernel(SviGemmArgs g) {
+    __shared__ f32x4s red[NW][MB][64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int r16 = lane & 15, kg = lane >> 4;
+    const int n0 = blockIdx.x * 16;
+    const int kq = g.K / NW, kbeg = wave * kq, kend = kbeg + kq;          // K % (32 NW) == 0: every share is a whole number of 32-steps
+    const u32x2* wp = reinterpret_cast<const u32x2*>(reinterpret_cast<const unsigned char*>(g.W) + (size_t)min(n0 + r16, g.N - 1) * g.ldw + 8 * kg);      // wp[i]: the 8 bytes at k + 8 i
+    const bf16* ap[MB];
+#pragma unroll
+    for (int b = 0; b < MB; ++b) ap[b] = g.A + (size_t)min(16 * b + r16, g.M - 1) * g.lda + 8 * kg;
+    f32x4s acc[MB];
+#pragma unroll
+    for (int b = 0; b < MB; ++b) acc[b] = f32x4s{0.f, 0.f, 0.f, 0.f};
+    int k = kbeg;
+    for (; k + 32 * UN <= kend; k += 32 * UN) {                  // UN K steps requested together, then consumed
+        u32x2 wf[UN];
+        bf16x8 af[UN][MB];
+#pragma unroll
+        for (int u = 0; u < UN; ++u) wf[u] = wp[(k >> 3) + 4 * u];          // the HBM stream first
+#pragma unroll
+        for (int u = 0; u < UN; ++u)
+#pragma unroll
+            for (int b = 0; b < MB; ++b) af[u][b] = ld_bf16x8(ap[b] + k + 32 * u);
+        __builtin_amdgcn_sched_barrier(0);                        // all requests out before the first wait (hipcc would interleave them with the MFMAs)
+#pragma unroll
+        for (int u = 0; u < UN; ++u)
+#pragma unroll
+            for (int b = 0; b < MB; ++b) acc[b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, e4m3x8_to_bf16x8(wf[u])), af[u][b], acc[b], 0, 0, 0);
+    }
+    for (; k < kend; k += 32) {
+        const bf16x8 wf = __builtin_bit_cast(bf16x8, e4m3x8_to_bf16x8(wp[k >> 3]));
+#pragma unroll
+        for (int b = 0; b < MB; ++b) acc[b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, ld_bf16x8(ap[b] + k), acc[b], 0, 0, 0);
+    }
+#pragma unroll
+    for (int b = 0; b < MB; ++b) red[wave][b][lane] = acc[b];
+    __syncthreads();
+    for (int idx = tid; idx < MB * 64; idx += 64 * NW) {
+        const int b = idx >> 6, l = idx & 63;
+        f32x4s s = red[0][b][l];
+#pragma unroll
+        for (int w = 1; w < NW; ++w) s += red[w][b][l];
+        const int m = 16 * b + (l & 15), n = n0 + 4 * (l >> 4);
+        if (m >= g.M || n >= g.N) continue;
+        bf16x4 o;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            float y = s[e];
+            if (n + e < g.N) {
+                if (g.bias) y += (float)g.bias[n + e];
+                y = rbf(y);
+                if (g.epi == SVI_EPI_BIAS_GATE_RES) {
+                    if (g.gate) y = rbf(g.gate[n + e] * y);
+                    y += (float)g.res[(size_t)m * g.ldres + n + e];
+                }
+            }
+            o[e] = (bf16)y;
+        }
+        if (n + 4 <= g.N) *reinterpret_cast<bf16x4*>(g.C + (size_t)m * g.ldc + n) = o;
+        else
+            for (int e = 0; e < 4 && n + e < g.N; ++e) g.C[(size_t)m * g.ldc + n + e] = o[e];
+    }
+}
+
 // =================================================================================================
 // MX-fp8 path (opt-in; never the default): C[M,N] = epi(A8[M,K] · W8[N,K]^T) on v_mfma_scale_f32_32x32x64_f8f6f4 — OCP e4m3
 // elements with one E8M0 power-of-two scale per 32 consecutive K elements, dequantised inside the matrix pipe at twice the bf16
@@ -1145,10 +1441,19 @@ static int gemm_device_cus() {
     return n;
 }
 
-svi_status svi_launch_gemm(const SviGemmArgs& g, hipStream_t st) {
+// The kernel the e4m3-operand launch takes (svi_gemm_w8_plan): svi_gemm_choose's answer where that kernel has an e4m3 form — the skinny kernel (W stored as
+// e4m3 only) and the 128^2 tile; the LDS-DMA fed 256-row tiles (192 / 259 / 260) have none and run on the 128^2 tile (DESIGN.md, FP8-resident weights).
+int svi_gemm_choose_e8(const SviGemmArgs& g, int ncu, int e8) {
+    const int kind = svi_gemm_choose(g, ncu);
+    return kind == 0 && e8 == 1 ? 0 : 128;
+}
+
+// e8: 0 = both operands bf16; 1 = W (and W2) stored as e4m3 bytes, ldw in bytes; 2 = A stored as e4m3 bytes, lda in bytes (svi_launch_gemm_e8)
+static svi_status launch_gemm(const SviGemmArgs& g, int e8, hipStream_t st) {
     SVI_REQUIRE(g.M >= 0 && g.N >= 0 && g.K > 0, "gemm: bad sizes M=%d N=%d K=%d", g.M, g.N, g.K);
     if (g.M == 0 || g.N == 0) return SVI_OK;
     SVI_REQUIRE(g.K % 8 == 0, "gemm: K=%d must be a multiple of 8", g.K);
+    if (e8) SVI_REQUIRE((e8 == 1 ? g.ldw : g.lda) % 16 == 0, "gemm: the leading dimension of an e4m3 operand (%d bytes) must be a multiple of 16", e8 == 1 ? g.ldw : g.lda);
     SVI_REQUIRE(g.lda % 8 == 0 && g.ldw % 8 == 0 && g.ldc % 8 == 0, "gemm: leading dims must be multiples of 8");
     SVI_REQUIRE(g.lda >= g.K && g.ldw >= g.K && g.ldc >= g.N, "gemm: leading dims too small");
     SVI_REQUIRE(((uintptr_t)g.A % 16) == 0 && ((uintptr_t)g.W % 16) == 0 && ((uintptr_t)g.C % 16) == 0,
@@ -1158,7 +1463,7 @@ svi_status svi_launch_gemm(const SviGemmArgs& g, hipStream_t st) {
         SVI_REQUIRE(g.res != nullptr && g.ldres % 8 == 0 && ((uintptr_t)g.res % 16) == 0,
                     "gemm: gate/residual epilogue needs an aligned residual");
     }
-    const int kind = svi_gemm_choose(g, gemm_device_cus());
+    const int kind = e8 ? svi_gemm_choose_e8(g, gemm_device_cus(), e8) : svi_gemm_choose(g, gemm_device_cus());
     const SviSwitches& sw = svi_switches();
     if (g.rowss)
         SVI_REQUIRE(kind != 0 && g.N % 64 == 0 && g.epi == SVI_EPI_BIAS && !g.bias_along_m && !g.W2 && g.ldss >= g.M && ((uintptr_t)g.rowss % 4) == 0,
@@ -1176,8 +1481,8 @@ svi_status svi_launch_gemm(const SviGemmArgs& g, hipStream_t st) {
             a.W2 = nullptr; a.bias2 = nullptr; a.n_split = 0; a.N = g.n_split; a.sel_n = g.sel_n > 0 ? g.sel_n : g.n_split;      // (the per-projection shape: the same kernel, and bits, as two separate launches)
             b.W2 = nullptr; b.bias2 = nullptr; b.n_split = 0; b.W = g.W2; b.bias = g.bias2; b.N = g.N - g.n_split; b.C = g.C + g.n_split;
             b.res = g.res ? g.res + g.n_split : nullptr; b.gate = g.gate ? g.gate + g.n_split : nullptr; b.sel_n = a.sel_n;
-            SVI_TRY(svi_launch_gemm(a, st));
-            return svi_launch_gemm(b, st);
+            SVI_TRY(launch_gemm(a, e8, st));
+            return launch_gemm(b, e8, st);
         }
     }
     if (kind == 0) {
@@ -1185,7 +1490,9 @@ svi_status svi_launch_gemm(const SviGemmArgs& g, hipStream_t st) {
         const bool wide = g.K % 256 == 0;                 // eight K shares when they come out whole
 #define SVI_SKINNY(MB, UN)                                                                                                        \
         do {                                                                                                                     \
-            if (wide) hipLaunchKernelGGL((gemm_skinny_kernel<MB, 8, UN>), grid, dim3(512), 0, st, g);                              \
+            if (e8 && wide) hipLaunchKernelGGL((gemm_skinny_w8_kernel<MB, 8, UN>), grid, dim3(512), 0, st, g);                     \
+            else if (e8) hipLaunchKernelGGL((gemm_skinny_w8_kernel<MB, 4, UN>), grid, dim3(256), 0, st, g);                        \
+            else if (wide) hipLaunchKernelGGL((gemm_skinny_kernel<MB, 8, UN>), grid, dim3(512), 0, st, g);                         \
             else hipLaunchKernelGGL((gemm_skinny_kernel<MB, 4, UN>), grid, dim3(256), 0, st, g);                                   \
         } while (0)
         if (g.M <= 16) SVI_SKINNY(1, 8);
@@ -1221,6 +1528,20 @@ svi_status svi_launch_gemm(const SviGemmArgs& g, hipStream_t st) {
     const int tiles_m = (g.M + BM - 1) / BM, tiles_n = (g.N + BN - 1) / BN;
     // at most one workgroup per CU (the C1-size step's projections: 240 tiles): the loop with four K tiles of loads in flight; SVI_GEMM_PF = 1 | 4 forces one
     const bool deep = g.K % BK == 0 && g.K >= SVI_GEMM_DEEP_PF * BK && (sw.gemm_pf ? sw.gemm_pf > 1 : (long)tiles_m * tiles_n <= gemm_device_cus());
+    if (e8) {          // one operand stored as e4m3: the same two loops (the four-wave A/B form of the deep loop has no e4m3 twin; its bits are the eight-wave form's)
+#define SVI_E8_TILE(PF, NT, E8)                                                                                                   \
+        do {                                                                                                                     \
+            SVI_TRY(svi_ensure_lds(reinterpret_cast<const void*>((gemm_e8_nt_kernel<PF, NT, E8>)), 4 * STAGE_BYTES));             \
+            hipLaunchKernelGGL((gemm_e8_nt_kernel<PF, NT, E8>), dim3(tiles_m * tiles_n), dim3(NT), 4 * STAGE_BYTES, st, g, tiles_m, tiles_n); \
+        } while (0)
+        if (deep && e8 == 1) SVI_E8_TILE(SVI_GEMM_DEEP_PF, 512, 1);
+        else if (deep) SVI_E8_TILE(SVI_GEMM_DEEP_PF, 512, 2);
+        else if (e8 == 1) SVI_E8_TILE(1, 256, 1);
+        else SVI_E8_TILE(1, 256, 2);
+#undef SVI_E8_TILE
+        SVI_LAUNCH_CHECK();
+        return SVI_OK;
+    }
     if (deep) {
         if (sw.gemm_pf == 4) {          // (A/B: the four-wave form of the deep loop)
             SVI_TRY(svi_ensure_lds(reinterpret_cast<const void*>(gemm_bf16_nt_kernel<SVI_GEMM_DEEP_PF>), 4 * STAGE_BYTES));
@@ -1235,4 +1556,11 @@ svi_status svi_launch_gemm(const SviGemmArgs& g, hipStream_t st) {
     }
     SVI_LAUNCH_CHECK();
     return SVI_OK;
+}
+
+svi_status svi_launch_gemm(const SviGemmArgs& g, hipStream_t st) { return launch_gemm(g, 0, st); }
+svi_status svi_launch_gemm_e8(const SviGemmArgs& g, int e8, hipStream_t st) {
+    SVI_REQUIRE(e8 == 1 || e8 == 2, "gemm: e8 = %d (1: W stored as e4m3, 2: A stored as e4m3)", e8);
+    SVI_REQUIRE(e8 == 1 || (!g.W2 && !g.skinny), "gemm: an e4m3 A operand goes with one bf16 W on the tiled kernel");
+    return launch_gemm(g, e8, st);
 }

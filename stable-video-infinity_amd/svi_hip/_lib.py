@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SVI_HIP_LIB") or os.path.join(_HERE, "libsvi_hip.so")   # SVI_HIP_LIB: A/B a variant build (tools/build_variant.py)
 
 SVI_OK = 0
-SVI_BF16, SVI_F32, SVI_F16 = 0, 1, 2
+SVI_BF16, SVI_F32, SVI_F16, SVI_E4M3 = 0, 1, 2, 3
 EPI_BIAS, EPI_BIAS_GELU_TANH, EPI_BIAS_GATE_RES, EPI_BIAS_GELU_ERF, EPI_BIAS_SILU, EPI_BIAS_RELU = 0, 1, 2, 3, 4, 5
 
 # every symbol include/svi_hip.h declares: (name, restype, argtypes)
@@ -84,6 +84,7 @@ SYMBOLS = [
     ("svi_rmsnorm_rope_qk", _i32, [_vp, _i32, _i32, _i32, _vp, _vp, _f32, _f32, _f32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     ("svi_gemm_bf16", _i32, [_vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _i32, _vp]),
     ("svi_gemm_bf16_pair", _i32, [_vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp]),
+    ("svi_gemm_bf16_w8", _i32, [_vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp]),
     ("svi_cfg_step", _i32, [_vp, _vp, _vp, _i64, _f32, _f32, _vp]),
     ("svi_mx8_quantize", _i32, [_vp, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _vp]),
     ("svi_gemm_mx8", _i32, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _vp]),
@@ -94,7 +95,9 @@ SYMBOLS = [
     ("svi_fp8_e4m3_to_bf16", _i32, [_vp, _vp, _i64, _vp]),
     ("svi_f32_to_fp8_e4m3", _i32, [_vp, _i32, _vp, _i64, _vp]),
     ("svi_lora_merge_e4m3", _i32, [_vp, _i32, _i32, _vp, _vp, _i32, _i32, _f32, _vp]),
+    ("svi_gemm_bf16_skinny", _i32, [_vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _vp]),
     ("svi_gemm_plan", _i32, [_i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(_i32)]),
+    ("svi_gemm_w8_plan", _i32, [_i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(_i32)]),
     ("svi_attention_plan", _i32, [_i32, _i32, _i32, _i32, C.POINTER(_i32)]),
     ("svi_vae_conv_plan", _i32, [_i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(_i64)]),
     ("svi_vae_tile_order", _i32, [_i32, _i32, _i32, C.POINTER(_i64)]),

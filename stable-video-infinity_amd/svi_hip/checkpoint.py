@@ -64,12 +64,13 @@ def dit_storage(torch_dtype):
         _dit_storage = before
 
 
-def load_dit(paths: Union[str, Sequence[str]], cfg: dict = None, device="cuda", torch_dtype=None):
+def load_dit(paths: Union[str, Sequence[str]], cfg: dict = None, device="cuda", torch_dtype=None, fp8_resident=None):
     """A WanDiT bound to the tensors of a (sharded) safetensors checkpoint.  bf16 and float8_e4m3fn tensors are bound as stored (fp8
     through the exact bind-time cast); anything else is cast to bf16, the dtype the pipelines run the DiT in.  cfg=None: read off the shapes.
     torch_dtype=torch.float8_e4m3fn: the reference's FP8 storage mode from stock shards (load_models(torch_dtype=...), test_svi.py:337) —
     every parameter is stored as e4m3, cast on the device with torch's rounding (ops.f32_to_fp8_e4m3); None: as stored, unless the call runs inside a
-    dit_storage(...) block."""
+    dit_storage(...) block.  fp8_resident (default: False, or SVI_FP8_RESIDENT): e4m3 Linear weights of the blocks are bound as stored, without bf16
+    copies (WanDiT.bind)."""
     from .dit import WanDiT
     if torch_dtype is None:
         torch_dtype = _dit_storage
@@ -84,7 +85,7 @@ def load_dit(paths: Union[str, Sequence[str]], cfg: dict = None, device="cuda", 
     if cfg is None:
         cfg = infer_dit_config(sd)
     m = WanDiT(**cfg)
-    m.bind(sd)
+    m.bind(sd, fp8_resident=fp8_resident)
     return m
 
 

@@ -11,6 +11,8 @@ re-binds them on `rebind()` (call it after a LoRA merge or any operation that mo
 from __future__ import annotations
 
 import ctypes as C
+import os
+import re
 from typing import Dict, Optional, Tuple
 
 import torch
@@ -78,6 +80,17 @@ class PromptPins:
         return drop
 
 
+# The parameters an FP8-resident bind hands to the kernels as the stored e4m3 bytes themselves (svi_dit_bind_weight with SVI_E4M3): the 2-D Linear weights
+# inside blocks.* — all but a few MB of a checkpoint.  Everything else (norms, biases, modulation, embedders, head) is cast to bf16 as before.
+_FP8_RESIDENT_KEY = re.compile(r"^blocks\.\d+\.(self_attn\.[qkvo]|cross_attn\.([qkvo]|k_img|v_img)|ffn\.[02]|audio_cross_attn\.(q_linear|kv_linear|proj))\.weight$")
+
+
+def fp8_resident_default() -> bool:
+    """SVI_FP8_RESIDENT=1 (also true / yes / on) makes fp8_resident=True the default of bind / from_state_dict / load_dit / install: e4m3 parameters are then
+    bound as they are stored, so a benchmark or example can be timed both ways without an edit.  Unset, empty, 0 or anything else: False."""
+    return os.environ.get("SVI_FP8_RESIDENT", "").strip().lower() in ("1", "true", "yes", "on")
+
+
 class WanDiT:
     def __init__(self, dim: int, in_dim: int, ffn_dim: int, out_dim: int, text_dim: int, freq_dim: int, eps: float,
                  patch_size: Tuple[int, int, int], num_heads: int, num_layers: int, has_image_input: bool, enable_multitalk: bool = False):
@@ -93,7 +106,8 @@ class WanDiT:
         L.check(L.lib().svi_dit_create(C.byref(cfg), C.byref(h)), "svi_dit_create")
         self._h = h
         self._params: Dict[str, torch.Tensor] = {}
-        self._fp8_sources: Dict[str, torch.Tensor] = {}        # fp8-stored parameters whose bf16 copies are bound (FP8 storage mode)
+        self._fp8_sources: Dict[str, torch.Tensor] = {}        # fp8-stored parameters (FP8 storage mode): bf16 copies are bound, or — fp8_resident — they themselves
+        self._fp8_resident = False          # the last bind()'s mode; rebind() keeps it
         self._param_versions = []
         self._epoch = 0                     # host-side: moves on bind / rebind / context_cache(); part of a captured graph's key
         self._ffn_mx8 = False               # opt-in MX-fp8 MLP (ffn_fp8_mfma)
@@ -103,17 +117,17 @@ class WanDiT:
 
     # ---- construction -------------------------------------------------------------------------
     @classmethod
-    def from_state_dict(cls, state_dict: Dict[str, torch.Tensor], device="cuda", **cfg) -> "WanDiT":
+    def from_state_dict(cls, state_dict: Dict[str, torch.Tensor], device="cuda", fp8_resident: Optional[bool] = None, **cfg) -> "WanDiT":
         m = cls(**cfg)
         m.bind({k: (v.to(device=device) if v.dtype == torch.float8_e4m3fn else v.to(device=device, dtype=torch.bfloat16)).contiguous()
-                for k, v in state_dict.items()})
+                for k, v in state_dict.items()}, fp8_resident=fp8_resident)
         return m
 
     @classmethod
-    def from_module(cls, wan_model) -> "WanDiT":
-        """Borrow the parameters of a reference `WanModel` (already on the GPU, bf16)."""
+    def from_module(cls, wan_model, fp8_resident: Optional[bool] = None) -> "WanDiT":
+        """Borrow the parameters of a reference `WanModel` (already on the GPU, bf16 or float8_e4m3fn)."""
         m = cls(**config_of_module(wan_model))
-        m.bind(dict(wan_model.state_dict()))
+        m.bind(dict(wan_model.state_dict()), fp8_resident=fp8_resident)
         return m
 
     def check_module_in_place(self, wan_model) -> None:
@@ -139,27 +153,37 @@ class WanDiT:
             raise RuntimeError("svi_hip: pipe.dit lost parameters since install(): call svi_hip.install(pipe) again")
         if moved:
             self._fp8_sources = {}
-            self.bind({k: v for k, v in sd.items()})
+            self.bind({k: v for k, v in sd.items()}, fp8_resident=self._fp8_resident)
 
-    def bind(self, state_dict: Dict[str, torch.Tensor]) -> None:
+    def bind(self, state_dict: Dict[str, torch.Tensor], fp8_resident: Optional[bool] = None) -> None:
+        """fp8_resident (default: False, or SVI_FP8_RESIDENT): parameters that arrive as float8_e4m3fn and are Linear weights inside blocks.* are bound as the
+        e4m3 tensors themselves — no bf16 tensor is made for them, their GEMMs widen the stored bytes on the way into the matrix pipe (svi_gemm_bf16_w8; the
+        same bits as the bf16 cast).  A no-op for bf16 parameters."""
         lib = L.lib()
+        self._fp8_resident = fp8_resident_default() if fp8_resident is None else bool(fp8_resident)
         for name, t in state_dict.items():
+            dtype = L.SVI_BF16
             if t.is_cuda and t.dtype == torch.float8_e4m3fn:
-                # the reference's FP8 mode (test_svi.py:337): parameters live as e4m3 and are cast to bf16 in front of every use; the
-                # cast is exact, so it is done once here and the bf16 copy is what the kernels read (ops.fp8_e4m3_to_bf16)
-                from .ops import fp8_e4m3_to_bf16
                 self._fp8_sources[name] = t
-                t = fp8_e4m3_to_bf16(t)
-            if not t.is_cuda or t.dtype != torch.bfloat16 or not t.is_contiguous():
+                if self._fp8_resident and _FP8_RESIDENT_KEY.match(name) and t.dim() == 2 and t.shape[1] % 16 == 0 and t.is_contiguous():
+                    dtype = L.SVI_E4M3          # the stored bytes are what the kernels read: one byte per parameter, nothing cast
+                else:
+                    # the reference's FP8 mode (test_svi.py:337): parameters live as e4m3 and are cast to bf16 in front of every use; the
+                    # cast is exact, so it is done once here and the bf16 copy is what the kernels read (ops.fp8_e4m3_to_bf16)
+                    from .ops import fp8_e4m3_to_bf16
+                    t = fp8_e4m3_to_bf16(t)
+            if dtype == L.SVI_BF16 and (not t.is_cuda or t.dtype != torch.bfloat16 or not t.is_contiguous()):
                 raise RuntimeError(f"parameter {name} must be a contiguous CUDA bf16 tensor (got {t.device}, {t.dtype})")
             shape = (C.c_int64 * t.dim())(*t.shape)
-            L.check(lib.svi_dit_bind_weight(self._h, name.encode(), t.data_ptr(), L.SVI_BF16, shape, t.dim()),
+            L.check(lib.svi_dit_bind_weight(self._h, name.encode(), t.data_ptr(), dtype, shape, t.dim()),
                     f"bind {name}")
             self._params[name] = t
         self._audio_slots = {}              # svi_dit_bind_weight drops the audio slots: their projections were made with the old weights
         L.check(lib.svi_dit_check_bound(self._h), "svi_dit_check_bound")
         # what weights_changed() watches: the bound bf16 tensors and, in FP8 storage mode, the e4m3 tensors they were cast from
-        self._param_versions = [(t, _version(t)) for t in self._params.values()] + [(t, _version(t)) for t in self._fp8_sources.values()]
+        # (an FP8-resident parameter is both, once)
+        watched = {id(t): t for t in list(self._params.values()) + list(self._fp8_sources.values())}
+        self._param_versions = [(t, _version(t)) for t in watched.values()]
         self._epoch += 1
         if self._ffn_mx8:
             self.ffn_fp8_mfma(True)         # the e4m3 tensors may have moved with the re-bind
@@ -168,8 +192,17 @@ class WanDiT:
 
     def rebind(self) -> None:
         """Re-read every parameter's address (after a LoRA merge, .to(), an offload round trip ...); drops the context cache.
-        FP8-stored parameters are cast again from their e4m3 sources (an in-place update of a source is picked up)."""
-        self.bind({**self._params, **self._fp8_sources})
+        FP8-stored parameters are cast again from their e4m3 sources (an in-place update of a source is picked up); FP8-resident ones are
+        the bound tensors themselves and nothing is cast for them."""
+        self.bind({**self._params, **self._fp8_sources}, fp8_resident=self._fp8_resident)
+
+    def weight_bytes(self) -> Dict[str, int]:
+        """Bytes of the tensors the kernels read, by the format they are bound in: {"bf16": n, "e4m3": n}.  In FP8 storage mode without fp8_resident
+        every e4m3 parameter counts under "bf16" (its cast; the e4m3 source is alive beside it and is not what is bound)."""
+        out = {"bf16": 0, "e4m3": 0}
+        for t in self._params.values():
+            out["e4m3" if t.dtype == torch.float8_e4m3fn else "bf16"] += t.numel() * t.element_size()
+        return out
 
     def ffn_fp8_mfma(self, enable: bool = True) -> None:
         """Opt-in: run both MLP GEMMs of every block on the MX block-scaled fp8 matrix path (svi_gemm_mx8; ~2x the bf16 MFMA rate).

@@ -1027,7 +1027,7 @@ def _assert_resident(pipe, hip: WanDiT, full: bool = False) -> None:
 
 
 def install(pipe, vae: bool = True, encoders: bool = True, sampler: bool = True, resident: bool = True, vae_split=None, vae_group=None,
-            vae_encode_split=None):
+            vae_encode_split=None, fp8_resident=None):
     """Route `pipe`'s hot path (SVIVideoPipeline / WanVideoPipeline of the reference) through libsvi_hip.
 
     * `model_fn_wan_video` in the pipeline's defining module is replaced by the HIP-backed function
@@ -1052,6 +1052,8 @@ def install(pipe, vae: bool = True, encoders: bool = True, sampler: bool = True,
       before OR after its line 351.  288 GB of HBM holds every model; nothing is offloaded.  If offload is switched on behind install()'s back
       (the class's function called on the instance, a module moved to the CPU) the next clip refuses with a RuntimeError instead of computing
       on stale copies; parameters that merely moved on the device (a LoRA merge that re-created them) are re-bound.
+    * `fp8_resident` (default: False, or SVI_FP8_RESIDENT): a DiT whose parameters are float8_e4m3fn (test_svi.py:337) keeps its blocks' Linear weights as the
+      stored bytes — no bf16 copies (WanDiT.bind); the same bits, a third of the memory.
     """
     if resident:
         _make_resident(pipe)
@@ -1065,7 +1067,7 @@ def install(pipe, vae: bool = True, encoders: bool = True, sampler: bool = True,
     if off:
         raise RuntimeError(f"install(): the DiT must be on the GPU in bf16 (or FP8 storage) — {off[0]} is {dict(dit_module.named_parameters())[off[0]].device}/"
                            f"{dict(dit_module.named_parameters())[off[0]].dtype}; pipe.dit.to('cuda', torch.bfloat16) first, or install(pipe, resident=True)")
-    hip = WanDiT.from_module(dit_module)
+    hip = WanDiT.from_module(dit_module, fp8_resident=fp8_resident)
     _route_dit(pipe, hip, sampler=sampler)
     if vae and getattr(pipe, "vae", None) is not None:
         from .vae import WanVideoVAE, _encode_split_setting

@@ -700,6 +700,35 @@ svi_status svi_clip_check_bound(svi_clip* h);
 svi_status svi_clip_tokens(svi_clip* h, int32_t* tokens, int32_t* dim);
 svi_status svi_clip_encode_image(svi_clip* h, const float* images, int32_t B, int32_t H, int32_t W, float* out, svi_stream stream);
 
+/* The talk variant's audio encoder: wav2vec2-base (chinese-wav2vec2-base) as utils/audio_process.py:18-41 get_embedding runs it around
+ * utils/src/audio_analysis/wav2vec2.py Wav2Vec2Model.forward(input_values, seq_len, output_hidden_states=True), fp32 throughout (the reference
+ * runs it in fp32 on the CPU).  Waveform normalisation to zero mean / unit variance; seven bias-free Conv1d (kernels 10,3,3,3,3,2,2, strides
+ * 5,2,2,2,2,2,2) with GroupNorm(C, C) after the first and exact GELU after each; linear interpolation to seq_len frames (align_corners=True);
+ * LayerNorm + Linear; x + GELU(grouped positional Conv1d, padding k/2, last sample of an even kernel dropped); LayerNorm; num_layers post-norm
+ * blocks.  Weight names are the Hugging Face Wav2Vec2Model's state-dict keys, fp32, borrowed; the positional convolution's weight norm is folded
+ * by the caller into "encoder.pos_conv_embed.conv.weight" [hidden, hidden / pos_groups, pos_kernel]; "masked_spec_embed" is accepted and ignored.
+ *   svi_w2v_frames: host-only; frames the convolution stack makes of n_samples samples (0: fewer than its 400-sample receptive field).
+ *   svi_w2v_forward: samples f32 [n_samples] on the device (16 kHz mono, loudness-normalised by the caller), seq_len = int(n_samples / 16000 * 25)
+ *     -> out [seq_len, num_layers, hidden] fp32 or bf16 (out_dtype): block l's output at frame t in out[t][l] — what WanDiT's audio windows are
+ *     cut from.  Refused with a message, before anything runs: seq_len > 2048 (the encoder attention's key limit, about 81 s of audio), seq_len < 1,
+ *     n_samples < 1 or below the receptive field, an unbound weight.  svi_w2v_create refuses a head size the encoder attention does not have.
+ *   svi_w2v_forward_stage: the same forward up to one intermediate tensor, copied to out (f32, capacity values) — 0: normalised waveform [n];
+ *     1..7: convolution layer output [frames_i, conv_dim]; 8: interpolated [seq_len, conv_dim]; 9: feature projection [seq_len, hidden];
+ *     10: the positional convolution's own output; 11: the encoder's first LayerNorm; 12 + l: block l.  For tests and inspection. */
+typedef struct svi_w2v_config {
+    int32_t conv_dim, hidden, ffn, num_heads, num_layers, pos_kernel, pos_groups;
+    float eps;
+} svi_w2v_config;
+typedef struct svi_w2v svi_w2v;
+svi_status svi_w2v_create(const svi_w2v_config* cfg, svi_w2v** out);
+svi_status svi_w2v_destroy(svi_w2v* h);
+svi_status svi_w2v_bind_weight(svi_w2v* h, const char* name, const void* dev_ptr, svi_dtype dtype, const int64_t* shape, int32_t rank);
+svi_status svi_w2v_check_bound(svi_w2v* h);
+svi_status svi_w2v_frames(int64_t n_samples, int64_t* out);
+svi_status svi_w2v_forward(svi_w2v* h, const float* samples, int64_t n_samples, int32_t seq_len, void* out, svi_dtype out_dtype, svi_stream stream);
+svi_status svi_w2v_forward_stage(svi_w2v* h, const float* samples, int64_t n_samples, int32_t seq_len, int32_t stage, float* out, int64_t capacity,
+                                 svi_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

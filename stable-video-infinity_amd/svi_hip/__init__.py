@@ -13,9 +13,9 @@ from .vae import WanVideoVAE
 from .conditioning import condition_mask, condition_video, image_condition
 from .teacache import TeaCache
 from .pose import PoseEmbedder
-from .encoders import WanImageEncoder, WanTextEncoder
+from .encoders import WanAudioEncoder, WanImageEncoder, WanTextEncoder
 from . import checkpoint, lora, sequence_parallel
 from .stream import DanceStreamLoop, StreamLoop, TalkStreamLoop, u8_to_video, video_to_u8
 
 __all__ = ["WanDiT", "model_fn_wan_video", "model_fn_wan_talk_video", "cfg3_step_", "flash_attention", "fp8_attention", "fp8_attention_enabled", "layernorm_modulate", "rmsnorm_rope_", "linear",
-           "cfg_step_", "DenoiseLoop", "generate_noise", "install", "FlowMatchScheduler", "WanVideoVAE", "condition_mask", "condition_video", "image_condition", "TeaCache", "PoseEmbedder", "WanTextEncoder", "WanImageEncoder", "StreamLoop", "TalkStreamLoop", "DanceStreamLoop", "pose_window", "video_to_u8", "u8_to_video", "_lib"]
+           "cfg_step_", "DenoiseLoop", "generate_noise", "install", "FlowMatchScheduler", "WanVideoVAE", "condition_mask", "condition_video", "image_condition", "TeaCache", "PoseEmbedder", "WanTextEncoder", "WanImageEncoder", "WanAudioEncoder", "StreamLoop", "TalkStreamLoop", "DanceStreamLoop", "pose_window", "video_to_u8", "u8_to_video", "_lib"]

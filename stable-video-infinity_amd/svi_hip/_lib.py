@@ -35,6 +35,11 @@ class ClipConfig(C.Structure):
                 ("layers_used", _i32), ("norm_eps", _f32)]
 
 
+class W2vConfig(C.Structure):
+    _fields_ = [("conv_dim", _i32), ("hidden", _i32), ("ffn", _i32), ("num_heads", _i32), ("num_layers", _i32), ("pos_kernel", _i32),
+                ("pos_groups", _i32), ("eps", _f32)]
+
+
 SYMBOLS = [
     ("svi_last_error", C.c_char_p, []),
     ("svi_abi_version", _i32, []),
@@ -142,6 +147,13 @@ SYMBOLS = [
     ("svi_clip_check_bound", _i32, [_vp]),
     ("svi_clip_tokens", _i32, [_vp, C.POINTER(_i32), C.POINTER(_i32)]),
     ("svi_clip_encode_image", _i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp]),
+    ("svi_w2v_create", _i32, [C.POINTER(W2vConfig), C.POINTER(_vp)]),
+    ("svi_w2v_destroy", _i32, [_vp]),
+    ("svi_w2v_bind_weight", _i32, [_vp, C.c_char_p, _vp, _i32, C.POINTER(_i64), _i32]),
+    ("svi_w2v_check_bound", _i32, [_vp]),
+    ("svi_w2v_frames", _i32, [_i64, C.POINTER(_i64)]),
+    ("svi_w2v_forward", _i32, [_vp, _vp, _i64, _i32, _vp, _i32, _vp]),
+    ("svi_w2v_forward_stage", _i32, [_vp, _vp, _i64, _i32, _i32, _vp, _i64, _vp]),
 ]
 
 _lib = None

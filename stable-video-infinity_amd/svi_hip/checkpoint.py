@@ -121,3 +121,17 @@ def load_image_encoder(path: str, device="cuda"):
     WanImageEncoder's own state dict ("model.visual." keys) — WanImageEncoderStateDictConverter.from_civitai, image_encoder:894-902."""
     from .encoders import WanImageEncoder
     return WanImageEncoder.from_state_dict(_load_any(path, device), device=device, num_heads=16)
+
+
+def load_audio_encoder(path: str, device="cuda"):
+    """svi_hip.WanAudioEncoder from a Hugging Face wav2vec2 directory (chinese-wav2vec2-base): config.json plus model.safetensors or
+    pytorch_model.bin (a torch pickle of the state dict).  Weight-norm keys of either spelling are folded at bind time."""
+    import json
+    import os
+    from .encoders import WanAudioEncoder
+    with open(os.path.join(path, "config.json")) as f:
+        config = json.load(f)
+    for name in ("model.safetensors", "pytorch_model.bin"):
+        if os.path.exists(os.path.join(path, name)):
+            return WanAudioEncoder.from_state_dict(_load_any(os.path.join(path, name), device), config, device=device)
+    raise FileNotFoundError(f"{path}: neither model.safetensors nor pytorch_model.bin")

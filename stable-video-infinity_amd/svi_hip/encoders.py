@@ -174,3 +174,148 @@ class WanImageEncoder:
                 self._h = None
         except Exception:
             pass
+
+
+W2V_CONV_KERNEL, W2V_CONV_STRIDE = (10, 3, 3, 3, 3, 2, 2), (5, 2, 2, 2, 2, 2, 2)
+W2V_STAGES = dict(wave=0, interp=8, proj=9, pos=10, enc_ln=11)          # conv layer i: 1 + i; block l: 12 + l (svi_w2v_forward_stage)
+_W2V_POS = "encoder.pos_conv_embed.conv."
+
+
+def audio_frames(n_samples: int) -> int:
+    """Frames the wav2vec2 convolution stack makes of n_samples samples (host only: no GPU needed); 0 below its 400-sample receptive field."""
+    out = C.c_int64(0)
+    L.check(L.lib().svi_w2v_frames(int(n_samples), C.byref(out)), "svi_w2v_frames")
+    return out.value
+
+
+def fold_weight_norm(state_dict: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """The positional convolution's weight norm (nn.utils.weight_norm(conv, name="weight", dim=2)) folded into a plain
+    "encoder.pos_conv_embed.conv.weight" = v * g / ||v|| with the norm over all dimensions but the kernel's, in fp32.  Both spellings are read:
+    weight_g / weight_v (torch.nn.utils.weight_norm) and parametrizations.weight.original0 / original1 (the parametrization API).  A state dict
+    that already holds the plain weight is returned as it is.  Folded on the host whatever device the pair arrives on: one checkpoint gives the same
+    bits whether it was read to the CPU or straight into HBM."""
+    sd = dict(state_dict)
+    for g_key, v_key in ((_W2V_POS + "weight_g", _W2V_POS + "weight_v"),
+                         (_W2V_POS + "parametrizations.weight.original0", _W2V_POS + "parametrizations.weight.original1")):
+        if g_key in sd or v_key in sd:
+            if g_key not in sd or v_key not in sd:
+                raise KeyError(f"audio encoder: {g_key} and {v_key} come as a pair")
+            g, v = sd.pop(g_key).float().cpu(), sd.pop(v_key).float().cpu()
+            if g.dim() != 3 or g.shape[0] != 1 or g.shape[1] != 1 or g.shape[2] != v.shape[2]:
+                raise ValueError(f"audio encoder: weight norm over dim 2 expected, g is {tuple(g.shape)} for v {tuple(v.shape)}")
+            sd[_W2V_POS + "weight"] = v * (g / v.pow(2).sum(dim=(0, 1), keepdim=True).sqrt())
+    return sd
+
+
+class WanAudioEncoder:
+    """The talk variant's audio encoder on the device: wav2vec2-base as utils/audio_process.py:18-41 get_embedding runs it
+    (utils/src/audio_analysis/wav2vec2.py Wav2Vec2Model.forward with seq_len and output_hidden_states=True), fp32; parameters are fp32 copies
+    owned here.  The input is the ALREADY loudness-normalised 16 kHz mono array: loudness normalisation (pyloudnorm) and reading wav / mp4 files
+    stay with the caller."""
+
+    def __init__(self, conv_dim=512, hidden=768, ffn=3072, num_heads=12, num_layers=12, pos_kernel=128, pos_groups=16, eps=1e-5):
+        self.conv_dim, self.hidden, self.ffn, self.num_heads, self.num_layers = conv_dim, hidden, ffn, num_heads, num_layers
+        self.pos_kernel, self.pos_groups, self.eps = pos_kernel, pos_groups, eps
+        cfg = L.W2vConfig(conv_dim, hidden, ffn, num_heads, num_layers, pos_kernel, pos_groups, eps)
+        h = C.c_void_p()
+        L.check(L.lib().svi_w2v_create(C.byref(cfg), C.byref(h)), "svi_w2v_create")
+        self._h = h
+        self._params: Dict[str, torch.Tensor] = {}
+
+    @staticmethod
+    def config_from(config) -> dict:
+        """Constructor arguments from a Wav2Vec2Config, or the dict of its config.json; only the architecture this backend runs is accepted."""
+        get = (lambda k, d=None: config.get(k, d)) if isinstance(config, dict) else (lambda k, d=None: getattr(config, k, d))
+        dims = list(get("conv_dim", (512,) * 7))
+        if tuple(get("conv_kernel", W2V_CONV_KERNEL)) != W2V_CONV_KERNEL or tuple(get("conv_stride", W2V_CONV_STRIDE)) != W2V_CONV_STRIDE or \
+                len(set(dims)) != 1 or len(dims) != 7:
+            raise ValueError("audio encoder: the convolution stack must be seven layers of one width with kernels (10,3,3,3,3,2,2) and strides (5,2,2,2,2,2,2)")
+        if get("feat_extract_norm", "group") != "group" or get("conv_bias", False) or get("do_stable_layer_norm", False) or get("add_adapter", False):
+            raise ValueError("audio encoder: only the base layout is supported (group norm after the first convolution, bias-free convolutions, post-norm blocks, no adapter)")
+        if get("hidden_act", "gelu") != "gelu" or get("feat_extract_activation", "gelu") != "gelu":
+            raise ValueError("audio encoder: only the exact GELU activation is supported")
+        return dict(conv_dim=dims[0], hidden=get("hidden_size", 768), ffn=get("intermediate_size", 3072), num_heads=get("num_attention_heads", 12),
+                    num_layers=get("num_hidden_layers", 12), pos_kernel=get("num_conv_pos_embeddings", 128),
+                    pos_groups=get("num_conv_pos_embedding_groups", 16), eps=get("layer_norm_eps", 1e-5))
+
+    @classmethod
+    def from_state_dict(cls, state_dict: Dict[str, torch.Tensor], config, device="cuda") -> "WanAudioEncoder":
+        """state_dict: Wav2Vec2Model's keys (a "wav2vec2." prefix of a task head's checkpoint is stripped, its other keys are skipped); config: a
+        Wav2Vec2Config or the dict of config.json.  The positional convolution's weight norm is folded here (fold_weight_norm)."""
+        sd = {}
+        for k, v in state_dict.items():
+            if k.startswith("wav2vec2."):
+                k = k[len("wav2vec2."):]
+            if k.startswith(("feature_extractor.", "feature_projection.", "encoder.")):
+                sd[k] = v
+        m = cls(**cls.config_from(config))
+        m.bind({k: v.to(device=device, dtype=torch.float32).contiguous() for k, v in fold_weight_norm(sd).items()})
+        return m
+
+    @classmethod
+    def from_module(cls, hf_model, device="cuda") -> "WanAudioEncoder":
+        """An existing (reference) Wav2Vec2Model: its parameters are copied to fp32 tensors on the device."""
+        return cls.from_state_dict(dict(hf_model.state_dict()), hf_model.config, device=device)
+
+    def bind(self, state_dict: Dict[str, torch.Tensor]) -> None:
+        _bind_all(L.lib().svi_w2v_bind_weight, self._h, state_dict, torch.float32, L.SVI_F32, self._params, "audio encoder")
+        L.check(L.lib().svi_w2v_check_bound(self._h), "svi_w2v_check_bound")
+
+    @staticmethod
+    def _samples(speech) -> torch.Tensor:
+        x = torch.as_tensor(speech)
+        if x.dim() != 1:
+            raise ValueError(f"speech must be a 1-D array of samples (got {tuple(x.shape)})")
+        return x.to(device="cuda", dtype=torch.float32).contiguous()
+
+    @staticmethod
+    def seq_len(n_samples: int, sr: int = 16000) -> int:
+        """int(audio_duration * 25) of get_embedding (audio_process.py:19-20, :31), in its double arithmetic."""
+        return int(n_samples / sr * 25)
+
+    def encode(self, speech, sr: int = 16000, dtype: torch.dtype = torch.float32, seq_len: Optional[int] = None) -> torch.Tensor:
+        """speech: 1-D float tensor or ndarray, the loudness-normalised 16 kHz mono audio -> [N, num_layers, hidden] on the GPU (N = int(seconds * 25),
+        or seq_len: the reference class's own argument), fp32 or bf16: the `audio_emb` of TalkStreamLoop.run and WanDiT.stage_audio_windows."""
+        if sr != 16000:
+            raise ValueError(f"the audio encoder reads 16 kHz audio (got sr = {sr}); resample first")
+        if dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError(f"dtype must be torch.float32 or torch.bfloat16 (got {dtype})")
+        x = self._samples(speech)
+        n = x.numel()
+        S = self.seq_len(n, sr) if seq_len is None else int(seq_len)
+        out = torch.empty((max(S, 0), self.num_layers, self.hidden), dtype=dtype, device=x.device)
+        L.check(L.lib().svi_w2v_forward(self._h, L.ptr(x) or 16, n, S, L.ptr(out) or 16, L.SVI_F32 if dtype == torch.float32 else L.SVI_BF16,
+                                        L.current_stream()), "svi_w2v_forward")
+        return out
+
+    __call__ = encode
+
+    def stage(self, speech, stage, seq_len: Optional[int] = None) -> torch.Tensor:
+        """One intermediate tensor of encode(speech), fp32 (tests and inspection): stage = a W2V_STAGES name, ("conv", i) or ("layer", l)."""
+        x = self._samples(speech)
+        n = x.numel()
+        S = self.seq_len(n) if seq_len is None else int(seq_len)
+        if isinstance(stage, tuple):
+            kind, i = stage
+            code = {"conv": 1, "layer": 12}[kind] + int(i)
+            if kind == "conv":
+                frames = n
+                for k, s in list(zip(W2V_CONV_KERNEL, W2V_CONV_STRIDE))[:i + 1]:
+                    frames = (frames - k) // s + 1
+                shape = (frames, self.conv_dim)
+            else:
+                shape = (S, self.hidden)
+        else:
+            code = W2V_STAGES[stage]
+            shape = {"wave": (n,), "interp": (S, self.conv_dim)}.get(stage, (S, self.hidden))
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+        L.check(L.lib().svi_w2v_forward_stage(self._h, L.ptr(x), n, S, code, L.ptr(out), out.numel(), L.current_stream()), "svi_w2v_forward_stage")
+        return out
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None):
+                L.lib().svi_w2v_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass

@@ -141,8 +141,8 @@ class TalkStreamLoop(StreamLoop):
     converts to 8-bit frames and appends ALL of them to the video (`video_list += video`: clips are stitched whole).  Here the embedding [N, 12, 768]
     is uploaded once; at a clip boundary both audio slots of the DiT are cut and re-projected on the device where they stand
     (WanDiT.stage_audio_windows), so every clip after the first replays the first clip's step graph(s) on ONE DenoiseLoop(graph=True, resident=True);
-    the motion frames go through StreamLoop's 8-bit hand-off.  The audio encoder is outside: it runs once per audio file, its output is this
-    loop's input.  Clips chain, so there is no clip-per-rank mode; under a CFG pair the talk step's three forwards have no home and it is refused.
+    the motion frames go through StreamLoop's 8-bit hand-off.  The audio encoder runs once per audio file: its output is this loop's input, or
+    the loop runs it itself on the device (run(speech=, audio_encoder=), svi_hip.WanAudioEncoder).  Clips chain, so there is no clip-per-rank mode; under a CFG pair the talk step's three forwards have no home and it is refused.
     With sequence_parallel the loop keeps DenoiseLoop's eager shard forwards (the windows are cut on the device all the same, ops.audio_windows)."""
 
     def __init__(self, dit, vae, clip_encoder: Optional[Callable[[torch.Tensor], torch.Tensor]] = None, num_motion_frames: int = 1,
@@ -176,12 +176,27 @@ class TalkStreamLoop(StreamLoop):
         return k * self.num_frames - (self.num_motion_frames if k > 0 else 0)
 
     @torch.no_grad()
-    def run(self, input_frames_u8: torch.Tensor, ref_frame_u8: torch.Tensor, prompt: tuple, audio_emb: torch.Tensor, num_clips: int, seed=0,
-            clip_feature: Optional[torch.Tensor] = None, null_emb: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def run(self, input_frames_u8: torch.Tensor, ref_frame_u8: torch.Tensor, prompt: tuple, audio_emb: Optional[torch.Tensor] = None,
+            num_clips: Optional[int] = None, seed=0, clip_feature: Optional[torch.Tensor] = None, null_emb: Optional[torch.Tensor] = None, *,
+            speech=None, audio_encoder=None, audio_embedding: Optional[torch.Tensor] = None) -> torch.Tensor:
         """input_frames_u8 [n, H, W, 3] (the input image, n = 1), ref_frame_u8 [H, W, 3] (`random_ref_frame`, fixed for the stream), prompt =
-        (context_pos, context_neg) embeddings, audio_emb fp32 or bf16 [N, 12, 768]: the audio encoder's output for the whole stream (a stream that
-        outlasts it keeps reading its last row: the reference's clamp).  seed: one int for every clip (the reference's call) or one per clip.
-        null_emb: WanDiT.stage_audio_windows's.  Returns the stitched 8-bit video [num_clips * num_frames, H, W, 3] on the GPU: every clip whole."""
+        (context_pos, context_neg) embeddings, audio_emb (or audio_embedding=) fp32 or bf16 [N, 12, 768]: the audio encoder's output for the whole
+        stream (a stream that outlasts it keeps reading its last row: the reference's clamp).  Instead of the embedding: speech= the loudness-normalised
+        16 kHz mono samples (1-D tensor or ndarray) and audio_encoder= an svi_hip.WanAudioEncoder — encoded once per stream on the device
+        (get_embedding, utils/audio_process.py:18-41), the result never leaves HBM.  seed: one int for every clip (the reference's call) or one per
+        clip.  null_emb: WanDiT.stage_audio_windows's.  Returns the stitched 8-bit video [num_clips * num_frames, H, W, 3] on the GPU: every clip whole."""
+        if num_clips is None:
+            raise TypeError("TalkStreamLoop.run: num_clips is required")
+        if audio_embedding is not None:
+            if audio_emb is not None:
+                raise TypeError("TalkStreamLoop.run: audio_emb and audio_embedding name the same argument")
+            audio_emb = audio_embedding
+        if (speech is None) == (audio_emb is None):
+            raise TypeError("TalkStreamLoop.run: pass either the audio embedding or speech= with audio_encoder=")
+        if speech is not None:
+            if audio_encoder is None:
+                raise TypeError("TalkStreamLoop.run: speech= needs audio_encoder= (an svi_hip.WanAudioEncoder)")
+            audio_emb = audio_encoder.encode(speech)
         seeds = [int(seed)] * num_clips if isinstance(seed, int) else [int(s) for s in seed]
         if len(seeds) != num_clips:
             raise ValueError(f"{len(seeds)} seeds for {num_clips} clips")

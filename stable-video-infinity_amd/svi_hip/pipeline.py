@@ -8,6 +8,7 @@
 """
 from __future__ import annotations
 
+import contextlib
 import sys
 import types
 import weakref
@@ -50,6 +51,17 @@ TEA_GRAPH_BY_DEFAULT = True
 # consulted twice per step and so fills its budget sooner, computes a step before the positive one.  Four graphs hold these; a fifth triple evicts the
 # least recently used one, which is captured again if it returns (tests/test_gpu_talk3_tea.py cycles through more).
 TALK_TEA_GRAPHS = 4
+
+
+class _Clip:
+    """What DenoiseLoop.clip() yields: the tensors one clip's steps run on."""
+
+    def __init__(self, latents, ctx_pos, ctx_neg, cond, resident):
+        self.latents, self.ctx_pos, self.ctx_neg, self.cond, self.resident = latents, ctx_pos, ctx_neg, cond, resident
+
+    def result(self) -> torch.Tensor:
+        """The denoised latents: a resident loop's slot is the next clip's too, so a copy."""
+        return self.latents.clone() if self.resident else self.latents
 
 
 class DenoiseLoop:
@@ -192,6 +204,44 @@ class DenoiseLoop:
 
     def _owned(self, t) -> bool:
         return self.resident and t is not None and any(t is s for s in self._slots.values())
+
+    def stays_resident(self, tea: bool) -> bool:
+        """Whether a clip runs on the loop's own tensors: a resident loop, unless the clip's TeaCache steps take step()'s eager path."""
+        return self.resident and (not tea or self.tea_graph)
+
+    @contextlib.contextmanager
+    def clip(self, latents: torch.Tensor, ctx_pos: torch.Tensor, ctx_neg: Optional[torch.Tensor], cond: dict, resident: bool,
+             convert: Optional[Callable] = None, every_cond: bool = False, keep_cache: bool = False, audio_slots: bool = False):
+        """A clip's begin and end around its steps.  Yields a _Clip: the tensors the steps run on, and result() for what the clip returns.
+        `resident`: the context cache goes on if it is off and the inputs are copied into the loop's own tensors (adopt); the end leaves everything for
+        the next clip.  Otherwise the latents are cloned as contiguous bf16 (the caller's tensor stays untouched), the prompt embeddings and
+        clip_feature — with `every_cond` every tensor of `cond`: a captured step reads those very tensors — go through `convert` (default: contiguous
+        bf16 on the latents' device; install()'s samplers pass _stable_bf16), and the end drops the captured step, which read this clip's tensors and
+        cache entries.  `keep_cache` (install()'s samplers): the context cache is left as it is when on, and left on at the end; else it is switched
+        on for the clip and off behind it.  `audio_slots`: the talk clip's two staged slots go with the clip too."""
+        dit = self.dit
+        if resident:
+            if not dit._ctx_cache_on:
+                dit.context_cache(True)
+            run = _Clip(*self.adopt(latents, ctx_pos, ctx_neg, cond), resident=True)
+        else:
+            lat = latents.to(torch.bfloat16).contiguous().clone()
+            conv = convert or (lambda t: None if t is None else t.to(device=lat.device, dtype=torch.bfloat16).contiguous())
+            ctx_pos, ctx_neg = conv(ctx_pos), conv(ctx_neg)
+            cond = {k: conv(v) if isinstance(v, torch.Tensor) and (every_cond or k == "clip_feature") else v for k, v in cond.items()}
+            run = _Clip(lat, ctx_pos, ctx_neg, cond, resident=False)
+            if not (keep_cache and dit._ctx_cache_on):
+                dit.context_cache(True)
+        try:
+            yield run
+        finally:
+            if not resident:
+                self.drop_graph()
+                if audio_slots:
+                    dit.stage_audio(0, None)
+                    dit.stage_audio(1, None)
+                if not keep_cache:
+                    dit.context_cache(False)
 
     def close(self) -> None:
         """End of a resident stream: the captured step, the slots and the context cache go."""
@@ -457,16 +507,11 @@ class DenoiseLoop:
             self.dit.sp_group = self.sp_group
             fn = lambda *a, **kw: model_fn_wan_talk_video(*a, use_unified_sequence_parallel=True, **kw)      # noqa: E731
         self.scheduler.set_timesteps(num_inference_steps, denoising_strength=denoising_strength, shift=sigma_shift)
-        latents = latents.to(torch.bfloat16).contiguous().clone()
         ts_dev = self.scheduler.timesteps.to(device=latents.device, dtype=torch.float32)
-        ctx_pos = ctx_pos.to(device=latents.device, dtype=torch.bfloat16).contiguous()
-        ctx_neg = ctx_neg.to(device=latents.device, dtype=torch.bfloat16).contiguous()
-        if cond.get("clip_feature") is not None:
-            cond["clip_feature"] = cond["clip_feature"].to(device=latents.device, dtype=torch.bfloat16).contiguous()
         aud = tuple(a.to(device=latents.device, dtype=torch.bfloat16).contiguous() for a in audio_embed_tuple)
         aud0 = tuple(a.to(device=latents.device, dtype=torch.bfloat16).contiguous() for a in audio_embed_tuple_null)
-        self.dit.context_cache(True)
-        try:
+        with self.clip(latents, ctx_pos, ctx_neg, cond, resident=False) as run:      # the eager forwards read the tuples: nothing here is the loop's own
+            latents, ctx_pos, ctx_neg, cond = run.latents, run.ctx_pos, run.ctx_neg, run.cond
             for i, t in enumerate(progress_bar_cmd(self.scheduler.timesteps)):
                 tt, ds = ts_dev[i:i + 1], self.scheduler.step_delta(t)
                 c = fn(self.dit, latents, tt, ctx_pos, add_condition=add_condition, audio_embed_tuple=aud, tea_cache=tea_cache_posi, **cond)
@@ -476,9 +521,7 @@ class DenoiseLoop:
                     ops.cfg3_step_(latents, c, u, d, text_scale, audio_scale, ds)
                 else:
                     ops.cfg_step_(latents, c, None, 1.0, ds)
-        finally:
-            self.dit.context_cache(False)
-        return latents
+        return run.result()
 
     def _talk3_graphed(self, latents, timestep, ctx_pos, ctx_neg, cond, tea=None) -> None:
         """The three forwards of one talk step into self._cond / _uncond / _drop: the captured forward_talk3 call replayed, captured on first use
@@ -541,21 +584,11 @@ class DenoiseLoop:
         `tea`: (positive, negative) TeaCache objects, either may be None — the step's three decisions are taken first (_talk_tea_decide), then ONE
         forward_talk3(tea_modes) call runs, replayed from the graph of its mode triple (at most TALK_TEA_GRAPHS alive, the least recently used evicted);
         the two residual tensors are the loop's, slots on a resident loop.  talk_tea_counts counts the clip's steps per triple."""
-        resident = self.resident
-        dev = latents.device
-        if resident:
-            if not self.dit._ctx_cache_on:
-                self.dit.context_cache(True)
-            latents, ctx_pos, ctx_neg, cond = self.adopt(latents, ctx_pos, ctx_neg, {k: v for k, v in cond.items() if v is not None})
-        else:
-            latents = latents.to(torch.bfloat16).contiguous().clone()
-            ctx_pos = ctx_pos.to(device=dev, dtype=torch.bfloat16).contiguous()
-            ctx_neg = ctx_neg.to(device=dev, dtype=torch.bfloat16).contiguous()
-            # converted once: the captured step reads these very tensors
-            cond = {k: (v.to(device=dev, dtype=torch.bfloat16).contiguous() if isinstance(v, torch.Tensor) else v) for k, v in cond.items() if v is not None}
-            self.dit.context_cache(True)
-        ts_dev = timesteps.to(device=dev, dtype=torch.float32)
-        try:
+        ts_dev = timesteps.to(device=latents.device, dtype=torch.float32)
+        cond = {k: v for k, v in cond.items() if v is not None}
+        # (the talk step's TeaCache is always on the graphed path: a resident loop stays resident with it)
+        with self.clip(latents, ctx_pos, ctx_neg, cond, self.resident, every_cond=True, audio_slots=True) as c:
+            latents, ctx_pos, ctx_neg, cond = c.latents, c.ctx_pos, c.ctx_neg, c.cond
             if audio_embed_tuple is None and audio_embed_tuple_null is None:      # the caller staged the slots itself (WanDiT.stage_audio_windows)
                 if not self.dit.audio_staged(latents.shape[2]):
                     raise ValueError(f"sample_multitalk without audio tuples: the DiT's audio slots are not staged for {latents.shape[2]} latent frames "
@@ -574,13 +607,7 @@ class DenoiseLoop:
                 decided = None if tea is None else self._talk_tea_decide(latents, ts_dev[i:i + 1], tea[0], tea[1])
                 self._talk3_graphed(latents, ts_dev[i:i + 1], ctx_pos, ctx_neg, cond, decided)
                 ops.cfg3_step_(latents, self._cond, self._uncond, self._drop, text_scale, audio_scale, step_delta(timesteps[i]))
-        finally:
-            if not resident:
-                self.drop_graph()                 # the graph reads this clip's tensors, cache entries and audio slots: it dies with the clip
-                self.dit.stage_audio(0, None)
-                self.dit.stage_audio(1, None)
-                self.dit.context_cache(False)
-        return latents.clone() if resident else latents
+        return c.result()
 
     @torch.no_grad()
     def sample(self, latents: torch.Tensor, ctx_pos: torch.Tensor, ctx_neg: Optional[torch.Tensor],
@@ -597,28 +624,12 @@ class DenoiseLoop:
                        tea_cache_nega=TeaCache(num_inference_steps, tea_cache_l1_thresh, tea_cache_model_id))
         ts_dev = self.scheduler.timesteps.to(device=latents.device, dtype=torch.float32)
         self.tea_counts = {"computed": 0, "skipped": 0}
-        resident = self.resident and (not tea or self.tea_graph)
-        if resident:
-            # the clip's inputs go into the loop's own tensors; the context cache stays on from clip to clip (entries recomputed in place)
-            if not self.dit._ctx_cache_on:
-                self.dit.context_cache(True)
-            latents, ctx_pos, ctx_neg, cond = self.adopt(latents, ctx_pos, ctx_neg, cond)
-        else:
-            latents = latents.to(torch.bfloat16).contiguous().clone()
-            # the prompt embeddings are constants of the loop: project them (and every block's cross-attention K / V) once
-            ctx_pos = ctx_pos.to(device=latents.device, dtype=torch.bfloat16).contiguous()
-            ctx_neg = None if ctx_neg is None else ctx_neg.to(device=latents.device, dtype=torch.bfloat16).contiguous()
-            if "clip_feature" in cond and cond["clip_feature"] is not None:
-                cond["clip_feature"] = cond["clip_feature"].to(device=latents.device, dtype=torch.bfloat16).contiguous()
-            self.dit.context_cache(True)
-        try:
+        # the prompt embeddings are constants of the clip: projected (with every block's cross-attention K / V) once, under the context cache
+        with self.clip(latents, ctx_pos, ctx_neg, cond, self.stays_resident(bool(tea))) as c:
             for i, t in enumerate(progress_bar_cmd(self.scheduler.timesteps)):
-                self.step(latents, ts_dev[i:i + 1], self.scheduler.step_delta(t), ctx_pos, ctx_neg, cfg_scale, cond_wo_pose=cond_wo_pose, **tea, **cond)
-        finally:
-            if not resident:
-                self.drop_graph()                 # the graph reads this clip's tensors and cache entries: it dies with the clip
-                self.dit.context_cache(False)
-        return latents.clone() if resident else latents      # resident: the slot is the next clip's too
+                self.step(c.latents, ts_dev[i:i + 1], self.scheduler.step_delta(t), c.ctx_pos, c.ctx_neg, cfg_scale, cond_wo_pose=cond_wo_pose,
+                          **tea, **c.cond)
+        return c.result()
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -638,6 +649,12 @@ def _stable_bf16(hip: WanDiT, t: Optional[torch.Tensor]) -> Optional[torch.Tenso
             memo.clear()
         hit = memo[key] = (t, t.to(torch.bfloat16).contiguous())
     return hit[1]
+
+
+def _install_clip(hip: WanDiT) -> dict:
+    """How install()'s samplers begin and end a clip (DenoiseLoop.clip): conversions made once per tensor, at a stable address; the context cache
+    stays on from clip to clip, as under the swapped model_fn_wan_video."""
+    return dict(convert=lambda t: _stable_bf16(hip, t), every_cond=True, keep_cache=True)
 
 
 def _hip_model_fn(dit_module, x, timestep, context, clip_feature=None, y=None, tea_cache=None, add_condition=None,
@@ -705,32 +722,19 @@ def _hip_sample_with_regular_video(self, latents, prompt_emb_posi, prompt_emb_ne
                                               tea_cache_nega, usp_kwargs, use_controlnet, cfg_scale, progress_bar_cmd)
     _assert_resident(self, hip, full=True)           # once per clip: offload switched on / parameters moved since install()
     loop = self._svi_hip_loop
-    if not hip._ctx_cache_on:
-        hip.context_cache(True)
     tea = {}
     if (tea_cache_posi or {}).get("tea_cache") is not None:
         tea = dict(tea_cache_posi=tea_cache_posi["tea_cache"], tea_cache_nega=(tea_cache_nega or {}).get("tea_cache"))
-    resident = loop.resident and (not tea or loop.tea_graph)
     cond = {k: image_emb[k] for k in ("clip_feature", "y") if image_emb.get(k) is not None}
-    if resident:
-        # the rolling window re-enters __call__ per clip (test_svi.py:424-476): each clip's latents / prompt / conditioning are copied into the loop's
-        # own tensors, so clip k+1 replays the step graph clip k captured (DenoiseLoop.adopt)
-        lat, ctx_p, ctx_n, cond = loop.adopt(latents, prompt_emb_posi["context"], prompt_emb_nega["context"], cond)
-    else:
-        ctx_p = _stable_bf16(hip, prompt_emb_posi["context"])
-        ctx_n = _stable_bf16(hip, prompt_emb_nega["context"])
-        cond = {k: _stable_bf16(hip, v) for k, v in cond.items()}
-        lat = latents.contiguous().clone()               # the reference's loop leaves its input tensor untouched
     scale = float(cfg_scale["text"])
-    ts_dev = self.scheduler.timesteps.to(device=lat.device, dtype=torch.float32)
-    try:
+    ts_dev = self.scheduler.timesteps.to(device=latents.device, dtype=torch.float32)
+    # the rolling window re-enters __call__ per clip (test_svi.py:424-476): a resident loop copies each clip's latents / prompt / conditioning into its
+    # own tensors, so clip k+1 replays the step graph clip k captured; the reference's loop leaves its input tensor untouched either way
+    with loop.clip(latents, prompt_emb_posi["context"], prompt_emb_nega["context"], cond, loop.stays_resident(bool(tea)), **_install_clip(hip)) as c:
         for progress_id, timestep in enumerate(progress_bar_cmd(self.scheduler.timesteps)):
-            loop.step(lat, ts_dev[progress_id:progress_id + 1], _step_delta_of(self.scheduler, self.scheduler.timesteps[progress_id]),
-                      ctx_p, ctx_n, scale, **tea, **cond)
-    finally:
-        if not resident:
-            loop.drop_graph()             # the captured step reads this clip's tensors: it dies with the clip (as DenoiseLoop.sample)
-    return lat.clone() if resident else lat
+            loop.step(c.latents, ts_dev[progress_id:progress_id + 1], _step_delta_of(self.scheduler, self.scheduler.timesteps[progress_id]),
+                      c.ctx_pos, c.ctx_neg, scale, **tea, **c.cond)
+    return c.result()
 
 
 def _talk_sampler_passes_through(hip, latents, prompt_emb_posi, prompt_emb_nega, image_emb, extra_input, tea_cache_posi, tea_cache_nega, usp_kwargs,
@@ -846,30 +850,20 @@ def _hip_wan_pipeline_call(self, *args, **kwargs):
         if not plain:
             return user_bar(timesteps)                 # the reference's loop, over the swapped model_fn_wan_video
         _assert_resident(self, hip, full=True)
-        if not hip._ctx_cache_on:
-            hip.context_cache(True)
         tea = {}
         if p.get("tea_cache_l1_thresh") is not None:  # as :262-263 builds them: the defining module's own TeaCache, one per branch
             TC = sys.modules[cls.__module__].TeaCache
             mk = lambda: TC(p["num_inference_steps"], rel_l1_thresh=p["tea_cache_l1_thresh"], model_id=p.get("tea_cache_model_id", ""))      # noqa: E731
             tea = dict(tea_cache_posi=mk(), tea_cache_nega=mk())
         cond = {k: img[k] for k in ("clip_feature", "y") if img.get(k) is not None}
-        resident = loop.resident and (not tea or loop.tea_graph)
         ctx_n = nega["context"] if cfg_scale != 1.0 else None
-        if resident:
-            x, ctx_p, ctx_n, cond = loop.adopt(lat, posi["context"], ctx_n, cond)
-        else:
-            x, ctx_p, ctx_n = lat.contiguous().clone(), _stable_bf16(hip, posi["context"]), _stable_bf16(hip, ctx_n)
-            cond = {k: _stable_bf16(hip, v) for k, v in cond.items()}
         # :267 hands the model the timestep in the pipeline's dtype: the bf16-ROUNDED value is what the time embedding sees
-        ts_dev = self.scheduler.timesteps.to(dtype=getattr(self, "torch_dtype", torch.float32)).to(device=x.device, dtype=torch.float32)
-        try:
+        ts_dev = self.scheduler.timesteps.to(dtype=getattr(self, "torch_dtype", torch.float32)).to(device=lat.device, dtype=torch.float32)
+        with loop.clip(lat, posi["context"], ctx_n, cond, loop.stays_resident(bool(tea)), **_install_clip(hip)) as c:
             for i, t in enumerate(user_bar(timesteps)):
-                loop.step(x, ts_dev[i:i + 1], _step_delta_of(self.scheduler, self.scheduler.timesteps[i]), ctx_p, ctx_n, cfg_scale, **tea, **cond)
-        finally:
-            if not resident:
-                loop.drop_graph()
-        seen["denoised"] = x.clone() if resident else x
+                loop.step(c.latents, ts_dev[i:i + 1], _step_delta_of(self.scheduler, self.scheduler.timesteps[i]), c.ctx_pos, c.ctx_neg, cfg_scale,
+                          **tea, **c.cond)
+        seen["denoised"] = c.result()
         return ()
 
     def decode_video(latents, *a, vae_split=None, vae_group=None, **k):

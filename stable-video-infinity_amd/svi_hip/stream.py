@@ -12,6 +12,7 @@ Outside SURVEY §8's path and therefore injected: the prompt embeddings (T5) and
 """
 from __future__ import annotations
 
+from types import SimpleNamespace
 from typing import Callable, List, Optional, Sequence
 
 import torch
@@ -40,7 +41,21 @@ def u8_to_video(frames: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def seeds_per_clip(seed, num_clips: int) -> List[int]:
+    """`seed` — one int for every clip, or one per clip — as the list of the clips' seeds."""
+    seeds = [int(seed)] * num_clips if isinstance(seed, int) else [int(s) for s in seed]
+    if len(seeds) != num_clips:
+        raise ValueError(f"{len(seeds)} seeds for {num_clips} clips")
+    return seeds
+
+
 class StreamLoop:
+    """The one clip walk (_walk).  A variant says what differs: the single-rank DenoiseLoop it runs on (`single_rank`), what clip k is sampled
+    with (_clip_inputs), which sampler runs (_sample), what the trace notes of the loop afterwards (_loop_trace), and whether a clip is stitched
+    whole (`stitch_whole`) or loses the motion frames it hands on."""
+    single_rank = dict(resident=True)      # every clip of the stream replays the step graph the first one captured
+    stitch_whole = False
+
     def __init__(self, dit, vae, clip_encoder: Optional[Callable[[torch.Tensor], torch.Tensor]] = None, num_motion_frames: int = 1,
                  num_frames: int = 81, num_inference_steps: int = 50, cfg_scale: float = 5.0, sigma_shift: float = 5.0,
                  ref_pad_cfg: bool = False, ref_pad_num: int = 0, seed_times: int = 42, tiled: bool = False, tile_size=(30, 52),
@@ -64,7 +79,7 @@ class StreamLoop:
             if vae_group is None and (vae_split is None or tuple(vae_split) != (1, 1)):
                 vae_group = latency_group(self.loop)
         else:
-            self.loop = DenoiseLoop(dit, resident=True)      # every clip of the stream replays the step graph the first one captured
+            self.loop = DenoiseLoop(dit, **self.single_rank)
         if vae_group is not None and vae_split is None:
             import torch.distributed as dist
             vae_split = default_vae_split(dist.get_world_size(vae_group))
@@ -88,20 +103,8 @@ class StreamLoop:
         [frames, H, W, 3] on the GPU: every clip but the last loses its final `num_motion_frames` frames.
         `start_clip`: resume a stream at clip index k (input_frames_u8 = the motion frames clip k-1 handed over): clips
         k .. num_clips-1 run with the seeds and prompts of their own indices."""
-        from .parallel import clip_prompt_index, clip_seed
-        motion = input_frames_u8.to("cuda")
-        ref = u8_to_video(ref_frame_u8.to("cuda")[None])[0]
-        H, W = motion.shape[1:3]
-        tlat = (self.num_frames - 1) // 4 + 1
-        pieces = []
-        self.trace = []
-        cache_was_on = self.loop.dit._ctx_cache_on
-        try:
-            self._clips(range(start_clip, num_clips), num_clips, motion, ref, prompts, prompt_repeat_times, use_first_prompt_only, clip_feature, pieces, H, W, tlat)
-        finally:
-            if not cache_was_on:
-                self.loop.close()      # the resident loop keeps the context cache on from clip to clip; hand the model back as it came
-        return torch.cat(pieces, dim=0)
+        return self._walk(range(start_clip, num_clips), num_clips, input_frames_u8, ref_frame_u8, clip_feature,
+                          SimpleNamespace(prompts=prompts, prompt_repeat_times=prompt_repeat_times, use_first_prompt_only=use_first_prompt_only))
 
     def _clip_feature(self, first: torch.Tensor, clip_feature: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
         """The CLIP feature of a clip's first motion frame, or the caller's when the loop has no encoder."""
@@ -111,25 +114,49 @@ class StreamLoop:
             return self.clip_encoder.encode_image([first[:1]]).to(torch.bfloat16)
         return self.clip_encoder(first[:1])
 
-    def _clips(self, clips, num_clips, motion, ref, prompts, prompt_repeat_times, use_first_prompt_only, clip_feature, pieces, H, W, tlat) -> None:
+    def _clip_inputs(self, k: int, run):
+        """What clip k is sampled with: (seed, (ctx_pos, ctx_neg), further keywords of the sampler — conditions —, further trace entries).  `run`:
+        what run() handed to _walk, plus the clip's tlat, H and W.  Called at the clip boundary, behind the conditioning encode."""
         from .parallel import clip_prompt_index, clip_seed
-        for k in clips:
-            first = u8_to_video(motion)                                          # preprocess_image of every motion frame
-            y = image_condition(self.vae, first, ref, self.num_frames, self.ref_pad_cfg, self.ref_pad_num, **self.vae_encode_split)
-            cf = self._clip_feature(first, clip_feature)
-            ctx_pos, ctx_neg = prompts[clip_prompt_index(k, len(prompts), prompt_repeat_times, use_first_prompt_only)]
-            seed = clip_seed(k, self.seed_times)
-            lat = generate_noise((1, 16, tlat, H // 8, W // 8), seed=seed, device="cpu", dtype=torch.float32).to("cuda", torch.bfloat16)
-            cond = dict(y=y)
-            if cf is not None:
-                cond["clip_feature"] = cf
-            lat = self.loop.sample(lat, ctx_pos, ctx_neg, num_inference_steps=self.steps, cfg_scale=self.cfg_scale,
-                                   sigma_shift=self.sigma_shift, **cond)
-            video = self.vae.decode(lat.float(), device="cuda", **self.tiler, **self.vae_split)[0]  # [3, num_frames, H, W] fp32
-            frames = video_to_u8(video)
-            self.trace.append(dict(clip=k, seed=seed, motion=motion, y=y, latents=lat, frames=frames))
-            motion = frames[-self.num_motion_frames:]
-            pieces.append(frames[:-self.num_motion_frames] if k < num_clips - 1 else frames)
+        prompt = run.prompts[clip_prompt_index(k, len(run.prompts), run.prompt_repeat_times, run.use_first_prompt_only)]
+        return clip_seed(k, self.seed_times), prompt, {}, {}
+
+    def _sample(self, lat, ctx_pos, ctx_neg, cond) -> torch.Tensor:
+        return self.loop.sample(lat, ctx_pos, ctx_neg, num_inference_steps=self.steps, cfg_scale=self.cfg_scale, sigma_shift=self.sigma_shift, **cond)
+
+    def _loop_trace(self) -> dict:
+        """Trace entries read off the loop once a clip is sampled."""
+        return {}
+
+    def _walk(self, clips, num_clips: int, input_frames_u8, ref_frame_u8, clip_feature, run) -> torch.Tensor:
+        """Clips `clips` of a stream of `num_clips`, stitched.  The model is handed back as it came, whatever ends the walk."""
+        motion = input_frames_u8.to("cuda")
+        ref = u8_to_video(ref_frame_u8.to("cuda")[None])[0]
+        run.H, run.W = H, W = motion.shape[1:3]
+        run.tlat = tlat = (self.num_frames - 1) // 4 + 1
+        pieces = []
+        self.trace = []
+        cache_was_on = self.loop.dit._ctx_cache_on
+        try:
+            for k in clips:
+                first = u8_to_video(motion)                                          # preprocess_image of every motion frame
+                y = image_condition(self.vae, first, ref, self.num_frames, self.ref_pad_cfg, self.ref_pad_num, **self.vae_encode_split)
+                cond = dict(y=y)
+                cf = self._clip_feature(first, clip_feature)
+                if cf is not None:
+                    cond["clip_feature"] = cf
+                seed, (ctx_pos, ctx_neg), more, noted = self._clip_inputs(k, run)
+                lat = generate_noise((1, 16, tlat, H // 8, W // 8), seed=seed, device="cpu", dtype=torch.float32).to("cuda", torch.bfloat16)
+                lat = self._sample(lat, ctx_pos, ctx_neg, dict(cond, **more))
+                video = self.vae.decode(lat.float(), device="cuda", **self.tiler, **self.vae_split)[0]  # [3, num_frames, H, W] fp32
+                frames = video_to_u8(video)
+                self.trace.append(dict(clip=k, seed=seed, motion=motion, y=y, latents=lat, frames=frames, **noted, **self._loop_trace()))
+                motion = frames[-self.num_motion_frames:]
+                pieces.append(frames if self.stitch_whole or k == num_clips - 1 else frames[:-self.num_motion_frames])
+        finally:
+            if not cache_was_on:
+                self.loop.close()      # the resident loop keeps the context cache on from clip to clip; hand the model back as it came
+        return torch.cat(pieces, dim=0)
 
 
 class TalkStreamLoop(StreamLoop):
@@ -144,6 +171,8 @@ class TalkStreamLoop(StreamLoop):
     the motion frames go through StreamLoop's 8-bit hand-off.  The audio encoder runs once per audio file: its output is this loop's input, or
     the loop runs it itself on the device (run(speech=, audio_encoder=), svi_hip.WanAudioEncoder).  Clips chain, so there is no clip-per-rank mode; under a CFG pair the talk step's three forwards have no home and it is refused.
     With sequence_parallel the loop keeps DenoiseLoop's eager shard forwards (the windows are cut on the device all the same, ops.audio_windows)."""
+    single_rank = dict(graph=True, resident=True)
+    stitch_whole = True                         # `video_list += video` in both branches of test_svi_talk.py:304-308: every clip whole
 
     def __init__(self, dit, vae, clip_encoder: Optional[Callable[[torch.Tensor], torch.Tensor]] = None, num_motion_frames: int = 1,
                  num_frames: int = 81, num_inference_steps: int = 50, cfg_scale: Optional[dict] = None, sigma_shift: float = 5.0,
@@ -166,8 +195,6 @@ class TalkStreamLoop(StreamLoop):
                          num_inference_steps=num_inference_steps, cfg_scale=cfg_scale, sigma_shift=sigma_shift, ref_pad_cfg=ref_pad_cfg,
                          ref_pad_num=ref_pad_num, tiled=tiled, tile_size=tile_size, tile_stride=tile_stride, vae_split=vae_split, vae_group=vae_group,
                          sp_group=sp_group, sequence_parallel=sequence_parallel, vae_encode_split=vae_encode_split)
-        if not sequence_parallel:
-            self.loop = DenoiseLoop(dit, graph=True, resident=True)
         self.tea = dict(tea_cache_l1_thresh=tea_cache_l1_thresh, tea_cache_model_id=tea_cache_model_id)
 
     def audio_start(self, k: int) -> int:
@@ -197,52 +224,35 @@ class TalkStreamLoop(StreamLoop):
             if audio_encoder is None:
                 raise TypeError("TalkStreamLoop.run: speech= needs audio_encoder= (an svi_hip.WanAudioEncoder)")
             audio_emb = audio_encoder.encode(speech)
-        seeds = [int(seed)] * num_clips if isinstance(seed, int) else [int(s) for s in seed]
-        if len(seeds) != num_clips:
-            raise ValueError(f"{len(seeds)} seeds for {num_clips} clips")
+        seeds = seeds_per_clip(seed, num_clips)
         if audio_emb.dim() != 3 or tuple(audio_emb.shape[1:]) != (12, 768) or audio_emb.shape[0] < 1:
             raise ValueError(f"audio_emb must be [N >= 1, 12, 768] (got {tuple(audio_emb.shape)})")
         emb = audio_emb.to("cuda")
         emb = (emb if emb.dtype in (torch.float32, torch.bfloat16) else emb.float()).contiguous()
         if null_emb is not None:
             null_emb = null_emb.to("cuda").contiguous()
-        motion = input_frames_u8.to("cuda")
-        ref = u8_to_video(ref_frame_u8.to("cuda")[None])[0]
-        H, W = motion.shape[1:3]
-        tlat = (self.num_frames - 1) // 4 + 1
-        ctx_pos, ctx_neg = prompt
-        scales = dict(text_scale=float(self.cfg_scale["text"]), audio_scale=float(self.cfg_scale["audio"]))
-        slots = self.loop.graph and (scales["text_scale"] != 1.0 or scales["audio_scale"] != 1.0)      # sample_multitalk's one-call step reads the slots
-        pieces = []
-        self.trace = []
-        cache_was_on = self.loop.dit._ctx_cache_on
-        try:
-            for k in range(num_clips):
-                first = u8_to_video(motion)
-                y = image_condition(self.vae, first, ref, self.num_frames, self.ref_pad_cfg, self.ref_pad_num, **self.vae_encode_split)
-                cf = self._clip_feature(first, clip_feature)
-                start = self.audio_start(k)
-                if slots:
-                    self.loop.dit.stage_audio_windows(emb, start, tlat, null_emb)
-                    aud = aud0 = None
-                else:
-                    aud, aud0 = self._tuples(emb, start, tlat), self._tuples(null_emb, start, tlat)
-                lat = generate_noise((1, 16, tlat, H // 8, W // 8), seed=seeds[k], device="cpu", dtype=torch.float32).to("cuda", torch.bfloat16)
-                cond = dict(y=y)
-                if cf is not None:
-                    cond["clip_feature"] = cf
-                lat = self.loop.sample_multitalk(lat, ctx_pos, ctx_neg, aud, aud0, num_inference_steps=self.steps, sigma_shift=self.sigma_shift,
-                                                 **scales, **self.tea, **cond)
-                video = self.vae.decode(lat.float(), device="cuda", **self.tiler, **self.vae_split)[0]
-                frames = video_to_u8(video)
-                self.trace.append(dict(clip=k, seed=seeds[k], audio_start=start, motion=motion, y=y, latents=lat, frames=frames,
-                                       captures=self.loop.captures, graphs=self.loop.held_graphs(), generation=self.loop.dit.generation()))
-                motion = frames[-self.num_motion_frames:]
-                pieces.append(frames)                   # `video_list += video` in both branches of test_svi_talk.py:304-308: every clip whole
-        finally:
-            if not cache_was_on:
-                self.loop.close()
-        return torch.cat(pieces, dim=0)
+        slots = self.loop.graph and any(s != 1.0 for s in self._scales().values())      # sample_multitalk's one-call step reads the slots
+        return self._walk(range(num_clips), num_clips, input_frames_u8, ref_frame_u8, clip_feature,
+                          SimpleNamespace(seeds=seeds, prompt=prompt, emb=emb, null_emb=null_emb, slots=slots))
+
+    def _scales(self) -> dict:
+        return dict(text_scale=float(self.cfg_scale["text"]), audio_scale=float(self.cfg_scale["audio"]))
+
+    def _clip_inputs(self, k: int, run):
+        start = self.audio_start(k)
+        if run.slots:
+            self.loop.dit.stage_audio_windows(run.emb, start, run.tlat, run.null_emb)
+            aud = aud0 = None
+        else:
+            aud, aud0 = self._tuples(run.emb, start, run.tlat), self._tuples(run.null_emb, start, run.tlat)
+        return run.seeds[k], run.prompt, dict(audio_embed_tuple=aud, audio_embed_tuple_null=aud0), dict(audio_start=start)
+
+    def _sample(self, lat, ctx_pos, ctx_neg, cond) -> torch.Tensor:
+        return self.loop.sample_multitalk(lat, ctx_pos, ctx_neg, num_inference_steps=self.steps, sigma_shift=self.sigma_shift, **self._scales(),
+                                          **self.tea, **cond)
+
+    def _loop_trace(self) -> dict:
+        return dict(captures=self.loop.captures, graphs=self.loop.held_graphs(), generation=self.loop.dit.generation())
 
     @staticmethod
     def _tuples(emb: Optional[torch.Tensor], start: int, tlat: int):
@@ -300,45 +310,27 @@ class DanceStreamLoop(StreamLoop):
         prompt = (context_pos, context_neg) embeddings, pose_u8 uint8 [N, h, w, 3]: the whole pose video at its source resolution (a stream that
         outlasts it wraps around; one shorter than a clip repeats).  seed: one int for every clip or one per clip (the script passes None: random).
         Returns the stitched 8-bit video on the GPU: every clip but the last loses its final `num_motion_frames` frames."""
-        seeds = [int(seed)] * num_clips if isinstance(seed, int) else [int(s) for s in seed]
-        if len(seeds) != num_clips:
-            raise ValueError(f"{len(seeds)} seeds for {num_clips} clips")
+        seeds = seeds_per_clip(seed, num_clips)
         if pose_u8.dtype != torch.uint8 or pose_u8.dim() != 4 or pose_u8.shape[0] < 1 or pose_u8.shape[3] != 3:
             raise ValueError(f"pose_u8 must be uint8 [N >= 1, h, w, 3] (got {pose_u8.dtype}, {tuple(pose_u8.shape)})")
-        motion = input_frames_u8.to("cuda")
-        H, W = motion.shape[1:3]
+        H, W = input_frames_u8.shape[1:3]
         tlat = (self.num_frames - 1) // 4 + 1
         pt, ph, pw = self.loop.dit.patch_size
         grid, pose_grid = (tlat // pt, H // 8 // ph, W // 8 // pw), self.pose_embedder.tokens(self.num_frames, H, W)
         if pose_grid != grid:
             raise ValueError(f"the pose embedder's token grid {pose_grid} for {self.num_frames} frames of {H} x {W} is not the DiT's {grid} for the clip's latents")
         pose = pose_u8.to("cuda").contiguous()                   # once per stream
-        ref = u8_to_video(ref_frame_u8.to("cuda")[None])[0]
-        ctx_pos, ctx_neg = prompt
-        pieces = []
-        self.trace = []
-        cache_was_on = self.loop.dit._ctx_cache_on
-        try:
-            for k in range(num_clips):
-                first = u8_to_video(motion)
-                y = image_condition(self.vae, first, ref, self.num_frames, self.ref_pad_cfg, self.ref_pad_num, **self.vae_encode_split)
-                cond = dict(y=y)
-                cf = self._clip_feature(first, clip_feature)
-                if cf is not None:
-                    cond["clip_feature"] = cf
-                if not self.remove_pose:
-                    cond["add_condition"] = self.pose_embedder.window(pose, k, self.num_frames, self.num_motion_frames, H, W)
-                lat = generate_noise((1, 16, tlat, H // 8, W // 8), seed=seeds[k], device="cpu", dtype=torch.float32).to("cuda", torch.bfloat16)
-                lat = self.loop.sample(lat, ctx_pos, ctx_neg, num_inference_steps=self.steps, cfg_scale=float(self.cfg_scale["text"]),
-                                       sigma_shift=self.sigma_shift, cond_wo_pose=self.cond_wo_pose, **self.tea, **cond)
-                video = self.vae.decode(lat.float(), device="cuda", **self.tiler, **self.vae_split)[0]
-                frames = video_to_u8(video)
-                self.trace.append(dict(clip=k, seed=seeds[k], pose_window=None if self.remove_pose else k, motion=motion, y=y,
-                                       add_condition=cond.get("add_condition"), latents=lat, frames=frames, captures=self.loop.captures,
-                                       graphs=self.loop.held_graphs()))
-                motion = frames[-self.num_motion_frames:]
-                pieces.append(frames[:-self.num_motion_frames] if k < num_clips - 1 else frames)
-        finally:
-            if not cache_was_on:
-                self.loop.close()
-        return torch.cat(pieces, dim=0)
+        return self._walk(range(num_clips), num_clips, input_frames_u8, ref_frame_u8, clip_feature, SimpleNamespace(seeds=seeds, prompt=prompt, pose=pose))
+
+    def _clip_inputs(self, k: int, run):
+        if self.remove_pose:
+            return run.seeds[k], run.prompt, {}, dict(pose_window=None, add_condition=None)
+        window = self.pose_embedder.window(run.pose, k, self.num_frames, self.num_motion_frames, run.H, run.W)
+        return run.seeds[k], run.prompt, dict(add_condition=window), dict(pose_window=k, add_condition=window)
+
+    def _sample(self, lat, ctx_pos, ctx_neg, cond) -> torch.Tensor:
+        return self.loop.sample(lat, ctx_pos, ctx_neg, num_inference_steps=self.steps, cfg_scale=float(self.cfg_scale["text"]),
+                                sigma_shift=self.sigma_shift, cond_wo_pose=self.cond_wo_pose, **self.tea, **cond)
+
+    def _loop_trace(self) -> dict:
+        return dict(captures=self.loop.captures, graphs=self.loop.held_graphs())

@@ -112,3 +112,15 @@ def test_pose_window_fails_loudly_without_gpu():
     if not torch.cuda.is_available():
         out = torch.zeros((3, 5, 16, 16))
         assert L.lib().svi_pose_window(pose.data_ptr(), out.data_ptr(), 4, 8, 8, 16, 16, 5, 1, 0, None) != 0 and L.last_error()
+
+
+def test_seeds_per_clip_is_one_seed_repeated_or_one_per_clip():
+    """The talk and the dance stream read their `seed` argument through one helper."""
+    from svi_hip.stream import seeds_per_clip
+    assert seeds_per_clip(7, 3) == [7, 7, 7] and seeds_per_clip(0, 1) == [0] and seeds_per_clip(5, 0) == []
+    got = seeds_per_clip([3, 45.0, torch.tensor(87)], 3)
+    assert got == [3, 45, 87] and all(type(s) is int for s in got)
+    assert seeds_per_clip((1, 2), 2) == [1, 2]
+    for seed, n in (([1], 2), ([1, 2, 3], 2), ([], 1)):
+        with pytest.raises(ValueError, match="seeds"):
+            seeds_per_clip(seed, n)

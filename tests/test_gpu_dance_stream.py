@@ -122,6 +122,30 @@ def test_pose_changes_the_stream():
     assert not torch.equal(outs[0], outs[1]) and not torch.equal(outs[1], outs[2]) and not torch.equal(outs[0], outs[2])
 
 
+def test_a_dance_stream_that_fails_midway_hands_the_model_back():
+    """The clip encoder raises at clip 1, behind clip 0's capture and context cache: run() passes the error on and leaves neither; the same loop object
+    then runs the stream as a newly built one does."""
+    import svi_hip
+    s, calls = _shared(), []
+
+    def encoder(first):
+        calls.append(first)
+        if len(calls) == 2:
+            raise RuntimeError("the clip encoder failed")
+        return s["clipf"]
+    mk = lambda enc: svi_hip.DanceStreamLoop(s["dit"], s["vae"], s["pose"], clip_encoder=enc, num_motion_frames=1, num_frames=NF,      # noqa: E731
+                                             num_inference_steps=2, cfg_scale=SCALES, ref_pad_num=-1)
+    sl = mk(encoder)
+    with pytest.raises(RuntimeError, match="the clip encoder failed"):
+        sl.run(s["img"], s["ref_frame"], s["prompt"], s["long"], 2, seed=5)
+    assert len(calls) == 2 and len(sl.trace) == 1 and sl.trace[0]["captures"] == 1                      # clip 0 ran, on a captured step
+    assert s["dit"]._ctx_cache_on is False and not s["dit"]._audio_slots and sl.loop.held_graphs() == []
+    again = sl.run(s["img"], s["ref_frame"], s["prompt"], s["long"], 2, seed=5)
+    fresh = mk(lambda first: s["clipf"]).run(s["img"], s["ref_frame"], s["prompt"], s["long"], 2, seed=5)
+    assert len(calls) == 4 and tuple(again.shape) == (NF - 1 + NF, H, W, 3) and torch.equal(again, fresh)
+    assert s["dit"]._ctx_cache_on is False
+
+
 def test_dance_stream_refusals():
     import svi_hip
     s = _shared()

@@ -68,6 +68,37 @@ def test_stream_loop_composition(n_motion):
     assert torch.equal(video, stitched)
 
 
+def test_a_stream_that_fails_midway_hands_the_model_back():
+    """The clip encoder raises at clip 1, behind clip 0's capture and context cache: run() passes the error on and leaves neither; the same loop object
+    then runs the stream as a newly built one does."""
+    import svi_hip
+    c = synth.TINY_DIT_I2V
+    sd = {k: torch.from_numpy(v) for k, v in synth.dit_state_dict(200, **c).items()}
+    dit = svi_hip.WanDiT.from_state_dict(sd, eps=1e-6, num_heads=synth.num_heads_of(c), **c)
+    vae = svi_hip.WanVideoVAE.from_state_dict({k: torch.from_numpy(v) for k, v in synth.vae_state_dict(500).items()})
+    H, W, NF, STEPS, CLIPS = 32, 48, 9, 2, 2
+    img = torch.from_numpy(synth.condition_frames(31, 1, H, W))
+    ref = torch.from_numpy(synth.condition_frames(32, 1, H, W)[0])
+    prompts = [(dev(synth.text_context(40 + i, 16, c["text_dim"], 9)), dev(synth.text_context(50 + i, 16, c["text_dim"], 5))) for i in range(2)]
+    clipf, calls = dev(synth.randn(33, 1, 257, 1280)), []
+
+    def encoder(first):
+        calls.append(first)
+        if len(calls) == 2:
+            raise RuntimeError("the clip encoder failed")
+        return clipf
+    mk = lambda enc: svi_hip.StreamLoop(dit, vae, clip_encoder=enc, num_motion_frames=1, num_frames=NF, num_inference_steps=STEPS, ref_pad_num=-1)      # noqa: E731
+    sl = mk(encoder)
+    with pytest.raises(RuntimeError, match="the clip encoder failed"):
+        sl.run(img, ref, prompts, CLIPS)
+    assert len(calls) == 2 and len(sl.trace) == 1 and sl.loop.captures == 1                             # clip 0 ran, on a captured step
+    assert dit._ctx_cache_on is False and not dit._audio_slots and sl.loop.held_graphs() == []
+    again = sl.run(img, ref, prompts, CLIPS)
+    fresh = mk(lambda first: clipf).run(img, ref, prompts, CLIPS)
+    assert len(calls) == 4 and tuple(again.shape) == (NF - 1 + NF, H, W, 3) and torch.equal(again, fresh)
+    assert dit._ctx_cache_on is False
+
+
 @pytest.mark.parametrize("case", synth.STREAM_CASES, ids=lambda c: c["name"])
 def test_stream_against_the_reference_clip_loop(case, golden):
     """Rows a23 / b against the reference itself: golden/clip_stream.npz holds what the reference's own clip loop (test_svi.py:424-485)

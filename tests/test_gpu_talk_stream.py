@@ -96,6 +96,30 @@ def test_talk_stream_is_the_hand_written_clip_loop(n_motion, steps, thresh):
     assert tr[2]["frames"].float().std() > 0
 
 
+def test_a_talk_stream_that_fails_midway_hands_the_model_back():
+    """The clip encoder raises at clip 1, behind clip 0's capture, staged audio slots and context cache: run() passes the error on and leaves none of
+    them; the same loop object then runs the stream as a newly built one does."""
+    import svi_hip
+    s, calls = _shared(), []
+
+    def encoder(first):
+        calls.append(first)
+        if len(calls) == 2:
+            raise RuntimeError("the clip encoder failed")
+        return s["clipf"]
+    mk = lambda enc: svi_hip.TalkStreamLoop(s["dit"], s["vae"], clip_encoder=enc, num_motion_frames=1, num_frames=NF, num_inference_steps=STEPS,      # noqa: E731
+                                            cfg_scale=SCALES, ref_pad_num=-1)
+    sl = mk(encoder)
+    with pytest.raises(RuntimeError, match="the clip encoder failed"):
+        sl.run(s["img"], s["ref_frame"], s["prompt"], s["emb"], 2, seed=5)
+    assert len(calls) == 2 and len(sl.trace) == 1 and sl.trace[0]["captures"] == 1                      # clip 0 ran, on a captured step
+    assert s["dit"]._ctx_cache_on is False and not s["dit"]._audio_slots and sl.loop.held_graphs() == []
+    again = sl.run(s["img"], s["ref_frame"], s["prompt"], s["emb"], 2, seed=5)
+    fresh = mk(lambda first: s["clipf"]).run(s["img"], s["ref_frame"], s["prompt"], s["emb"], 2, seed=5)
+    assert len(calls) == 4 and tuple(again.shape) == (2 * NF, H, W, 3) and torch.equal(again, fresh)
+    assert s["dit"]._ctx_cache_on is False and not s["dit"]._audio_slots
+
+
 def test_talk_stream_refusals():
     import svi_hip
     s = _shared()

@@ -7,6 +7,8 @@ output never leaves HBM (TalkStreamLoop.run(speech=, audio_encoder=)).  Added to
                                  (svi_hip.checkpoint.load_audio_encoder); no Hugging Face model class is imported or run
     --synthetic                  as there, and a random-init small encoder on a synthetic waveform (--audio_frames / 25 seconds of it) through the same path
     --audio_embedding FILE.npy   still accepted: the encoder's output made elsewhere, no encoder runs (what test_svi_talk_hip.py does)
+    --max_audio_frames N         the audio encoder's per-call frame limit (25 frames per second of audio).  Unset: 2048, about 81 s; longer audio needs
+                                 it raised (up to 65536, 43.7 min): the whole file is encoded in one call, as the reference does
 
     python examples/svi_talk_audio_hip.py --synthetic --num_clips 3 --num_steps 3 --height 32 --width 48 --max_frames 9
     python examples/svi_talk_audio_hip.py --dit_root weights/Wan2.1-I2V-14B-480P/ --talk_root weights/svi-talk.safetensors --audio_samples speech_16k.npy \\
@@ -34,10 +36,19 @@ def parse_args(argv=None):
     ap = argparse.ArgumentParser(add_help=False)
     ap.add_argument("--audio_samples", default=None, type=str, help="FILE.npy: float32 [n], the loudness-normalised 16 kHz mono samples (needs --wav2vec_path)")
     ap.add_argument("--wav2vec_path", default=None, type=str, help="directory of the audio encoder: config.json + model.safetensors or pytorch_model.bin")
+    ap.add_argument("--max_audio_frames", default=None, type=int, help="the audio encoder's frame limit per stream (default: 2048 frames, about 81 s of audio)")
     own, rest = ap.parse_known_args(argv)
     args = base.parse_args(rest)                 # everything else is test_svi_talk_hip.py's surface (its --help lists it)
-    args.audio_samples, args.wav2vec_path = own.audio_samples, own.wav2vec_path
+    args.audio_samples, args.wav2vec_path, args.max_audio_frames = own.audio_samples, own.wav2vec_path, own.max_audio_frames
     return args
+
+
+def check_audio_length(encoder, n_samples: int) -> None:
+    """Too long for the encoder's frame limit: say which flag raises it, before anything runs."""
+    rows = encoder.seq_len(n_samples)
+    if rows > encoder.max_frames:
+        raise SystemExit(f"the audio is {rows} frames ({n_samples / 16000:.1f} s), above the audio encoder's limit of {encoder.max_frames} frames; "
+                         f"pass --max_audio_frames {rows} (or more, up to {type(encoder).FRAME_CAP})")
 
 
 def audio_of(args, dev) -> dict:
@@ -49,13 +60,13 @@ def audio_of(args, dev) -> dict:
         if not args.wav2vec_path:
             raise SystemExit("--audio_samples needs --wav2vec_path DIR (the audio encoder's config.json and weights)")
         return dict(speech=np.load(args.audio_samples).astype(np.float32).reshape(-1),
-                    audio_encoder=svi_hip.checkpoint.load_audio_encoder(args.wav2vec_path, device=dev))
+                    audio_encoder=svi_hip.checkpoint.load_audio_encoder(args.wav2vec_path, device=dev, max_frames=args.max_audio_frames))
     if args.synthetic:
         import wav2vec_cases as wc
         rows = args.audio_frames or max(1, args.num_clips * args.max_frames - args.max_frames // 2)      # the last clip runs past the audio: the clamp holds the last row
         sd = {k: torch.from_numpy(v) for k, v in wc.state_dict(wc.SEEDS["talk_tiny"], wc.TALK_TINY).items()}
         return dict(speech=wc.waveform(3, max(400, rows * 640)),                                          # 640 samples = one video frame at 25 fps
-                    audio_encoder=svi_hip.WanAudioEncoder.from_state_dict(sd, wc.hf_config(wc.TALK_TINY), device=dev))
+                    audio_encoder=svi_hip.WanAudioEncoder.from_state_dict(sd, wc.hf_config(wc.TALK_TINY), device=dev, max_frames=args.max_audio_frames))
     raise SystemExit("audio is needed: --audio_samples FILE.npy with --wav2vec_path DIR, or --audio_embedding FILE.npy (or run with --synthetic)")
 
 
@@ -68,6 +79,8 @@ def main(argv=None) -> dict:
     dit, vae, clip_encoder, embed = base.synthetic_models(dev) if args.synthetic else base.real_models(args, dev)
     audio = audio_of(args, dev)
     on_device = "speech" in audio
+    if on_device:
+        check_audio_length(audio["audio_encoder"], len(audio["speech"]))
     rows = audio["audio_encoder"].seq_len(len(audio["speech"])) if on_device else int(audio["audio_embedding"].shape[0])
     height, width = (args.height // 16) * 16, (args.width // 16) * 16
     if args.synthetic:

@@ -710,7 +710,8 @@ svi_status svi_clip_encode_image(svi_clip* h, const float* images, int32_t B, in
  *   svi_w2v_frames: host-only; frames the convolution stack makes of n_samples samples (0: fewer than its 400-sample receptive field).
  *   svi_w2v_forward: samples f32 [n_samples] on the device (16 kHz mono, loudness-normalised by the caller), seq_len = int(n_samples / 16000 * 25)
  *     -> out [seq_len, num_layers, hidden] fp32 or bf16 (out_dtype): block l's output at frame t in out[t][l] — what WanDiT's audio windows are
- *     cut from.  Refused with a message, before anything runs: seq_len > 2048 (the encoder attention's key limit, about 81 s of audio), seq_len < 1,
+ *     cut from.  Refused with a message, before anything runs: seq_len above the handle's frame limit (2048, the resident encoder attention's key
+ *     count and about 81 s of audio, until svi_w2v_set_max_frames raises it), seq_len < 1,
  *     n_samples < 1 or below the receptive field, an unbound weight.  svi_w2v_create refuses a head size the encoder attention does not have.
  *   svi_w2v_forward_stage: the same forward up to one intermediate tensor, copied to out (f32, capacity values) — 0: normalised waveform [n];
  *     1..7: convolution layer output [frames_i, conv_dim]; 8: interpolated [seq_len, conv_dim]; 9: feature projection [seq_len, hidden];
@@ -728,6 +729,20 @@ svi_status svi_w2v_frames(int64_t n_samples, int64_t* out);
 svi_status svi_w2v_forward(svi_w2v* h, const float* samples, int64_t n_samples, int32_t seq_len, void* out, svi_dtype out_dtype, svi_stream stream);
 svi_status svi_w2v_forward_stage(svi_w2v* h, const float* samples, int64_t n_samples, int32_t seq_len, int32_t stage, float* out, int64_t capacity,
                                  svi_stream stream);
+/* Audio longer than 81 s (additive in ABI v13).  The reference encodes a file in ONE call, so a long file cannot be encoded in pieces.
+ *   svi_w2v_set_max_frames: the handle's per-call frame limit, 2048 when the handle is made; 1 .. 65536 (43.7 min at 25 frames per second), anything
+ *     else is refused with a message.  svi_w2v_forward and svi_w2v_forward_stage refuse a seq_len above the handle's limit (the message names the limit;
+ *     a handle at 2048 keeps the message above and names this call).  Up to 2048 frames the forward launches exactly what it launched before, bit for
+ *     bit, whatever the limit; above, its attention is the streaming kernel.  Also refused: a sample count or seq_len at which a launch with one thread
+ *     per value would pass 2^32 - 256 values (frames_1 * conv_dim; seq_len * max(conv_dim, hidden, ffn)) — 41 943 044 samples at conv_dim 512.
+ *   svi_encoder_attention_f32: the audio encoder's attention as an operator, O = softmax(scale Q K^T) V per head, fp32 operands on the device with
+ *     leading dimensions (floats between rows; head h is columns h D .. h D + D - 1), no bias table.  kernel 0: what the audio encoder launches
+ *     (resident up to 2048 keys, streaming above); 1: the resident kernel (whole score rows in LDS), refuses Lk > 2048; 2: the streaming kernel
+ *     (key tiles of 256, running maximum and sum, all fp32) at any Lk.  Refused with a message naming the argument, before any launch: D other than
+ *     32, 64, 80, 128; a null pointer; a leading dimension below heads * D; Lq, Lk or heads below 1; Lq or Lk above 65536; another kernel. */
+svi_status svi_w2v_set_max_frames(svi_w2v* h, int32_t max_frames);
+svi_status svi_encoder_attention_f32(const float* Q, int32_t ldq, const float* K, int32_t ldk, const float* V, int32_t ldv, float* O, int32_t ldo,
+                                     int32_t Lq, int32_t Lk, int32_t heads, int32_t D, float scale, int32_t kernel, svi_stream stream);
 
 #ifdef __cplusplus
 }

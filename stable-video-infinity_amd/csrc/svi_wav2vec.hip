@@ -17,6 +17,12 @@
 //
 // Compiled as ONE translation unit with svi_encoders.hip (included below; svi_hip/build.py lists this file in its place): the fp32 attention, LayerNorm
 // and GELU kernels this encoder launches are that file's, in its unnamed namespace, and stay there untouched — the same kernels, the same bits.
+//
+// Length: the reference hands the whole file to the model in one call (every frame attends to every other, the waveform statistics are the file's), so
+// a file cannot be encoded in pieces.  A handle serves up to max_frames frames per call: 2048 when it is made (the resident attention kernel's key
+// count, about 81 s), up to W2V_FRAME_CAP = 65536 (43.7 min) after svi_w2v_set_max_frames.  Up to 2048 frames the attention is the resident kernel,
+// above it the streaming kernel below (online softmax, fp32 throughout, LDS independent of the key count); nothing else in the forward
+// depends on the length.  svi_encoder_attention_f32 is that attention alone, as an operator.
 #include "svi_encoders.hip"
 
 namespace {
@@ -24,7 +30,9 @@ namespace {
 constexpr int W2V_CONVS = 7;
 const int W2V_KERNEL[W2V_CONVS] = {10, 3, 3, 3, 3, 2, 2};
 const int W2V_STRIDE[W2V_CONVS] = {5, 2, 2, 2, 2, 2, 2};
-constexpr int W2V_MAX_FRAMES = 2048;              // the encoder attention's key limit (svi_encoders.hip)
+constexpr int W2V_MAX_FRAMES = 2048;              // a fresh handle's frame limit: the resident encoder attention's key limit (svi_encoders.hip)
+constexpr int W2V_FRAME_CAP = 65536;              // the most svi_w2v_set_max_frames grants (43.7 min at 25 frames per second); the audit is in DESIGN §4
+constexpr long W2V_LAUNCH_ELEMS = 0xffffff00L;    // one thread per value, 256 per workgroup: the runtime launches at most 2^32 - 1 threads along x
 constexpr float W2V_GROUPNORM_EPS = 1e-5f;        // nn.GroupNorm's default (the model does not pass its layer_norm_eps there)
 constexpr float W2V_WAVE_EPS = 1e-7f;             // Wav2Vec2FeatureExtractor.zero_mean_unit_var_norm
 
@@ -197,9 +205,161 @@ __global__ void w2v_write_layer_kernel(const float* __restrict__ x, T* __restric
     out[((size_t)t * layers + layer) * dim + c] = (T)x[i];
 }
 
-// the fp32 pieces of svi_encoders.hip, by the names this file calls them
+// ---------------------------------------------------------------- streaming attention ----------------------------------------------
+// The encoder attention of svi_encoders.hip (enc_attention_kernel, ENC_RQ query rows per workgroup) for ANY key count, plain fp32 only — the audio
+// encoder past 2048 frames.  It lives here and not beside the resident kernel because that file is also the T5 / CLIP encoders' and stays byte for
+// byte what the committed profiles were collected on.  The key axis is walked in tiles of ENC_KT keys and a
+// query row keeps a running maximum m, a running sum l and an accumulator that is rescaled when the maximum moves (online softmax), so LDS and
+// registers do not grow with Lk.  One workgroup = one head x ENC_RQ query rows, as there.  Per tile:
+//   scores   thread <-> key: 16 dot products against the staged query rows; keys past Lk score -inf
+//   softmax  wave w owns rows 4w..4w+3: m' = max(m, tile max) (finite unless the caller's scores are -inf: a tile holds at least one key);
+//            alpha = exp(m - m'), 0 while m is still -inf (no (-inf) - (-inf)); p = exp(s - m'); l = l alpha + sum p
+//   P.V      thread <-> (row group, channel) as there: acc = acc alpha + sum_j p_j v_j, the tile's sum formed on its own in four interleaved chains
+// and O = acc / l after the last tile.  Every value is fp32; a term exp(s - m') that underflows is an exact zero and leaves acc and l as they were.
+// LDS: (16 D + 16 (ENC_KT + 1) + 48) x 4 B = 24.8 KiB at D = 128; registers: 16 score sums or 4 x RPG (<= 32) partial sums per thread.
+#define ENC_KT 256
+constexpr int ENC_KTP = ENC_KT + 1;               // row stride of the tile's scores: rows of two row groups in one wave fall on different banks
+template <int D>
+__global__ __launch_bounds__(256) void enc_attention_stream_kernel(const float* __restrict__ Q, int ldq, const float* __restrict__ K, int ldk,
+                                                                   const float* __restrict__ V, int ldv, float* __restrict__ O, int ldo, int Lq, int Lk,
+                                                                   float scale) {
+    __shared__ __attribute__((aligned(16))) float Qs[ENC_RQ * D];
+    __shared__ float S[ENC_RQ * ENC_KTP];
+    __shared__ float alpha_s[ENC_RQ], l_s[ENC_RQ];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, head = blockIdx.y, q0 = blockIdx.x * ENC_RQ;
+    const int nq = min(ENC_RQ, Lq - q0);
+    for (int i = tid; i < ENC_RQ * D; i += 256) {
+        const int r = i / D, c = i - r * D;
+        Qs[i] = r < nq ? Q[(size_t)(q0 + r) * ldq + head * D + c] : 0.f;
+    }
+    float m_run[4], l_run[4];                     // of rows 4 wave .. 4 wave + 3, the same in every lane of the wave
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { m_run[i] = -INFINITY; l_run[i] = 0.f; }
+    constexpr int NG = 256 / D, RPG = (ENC_RQ + NG - 1) / NG;
+    const int g = tid / D, c = tid - g * D;
+    float acc[RPG];
+#pragma unroll
+    for (int r = 0; r < RPG; ++r) acc[r] = 0.f;
+    __syncthreads();
+    for (int k0 = 0; k0 < Lk; k0 += ENC_KT) {
+        const int nk = min(ENC_KT, Lk - k0);
+        // ---- scores of this tile: thread <-> key
+        {
+            float s[ENC_RQ];
+#pragma unroll
+            for (int r = 0; r < ENC_RQ; ++r) s[r] = 0.f;
+            if (tid < nk) {
+                const float* kp = K + (size_t)(k0 + tid) * ldk + head * D;
+#pragma unroll 4
+                for (int cc = 0; cc < D; cc += 4) {
+                    float kv[4];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) kv[e] = kp[cc + e];
+#pragma unroll
+                    for (int r = 0; r < ENC_RQ; ++r) {
+                        const f32x4 qv = *reinterpret_cast<const f32x4*>(Qs + r * D + cc);
+                        s[r] = fmaf(qv[0], kv[0], s[r]); s[r] = fmaf(qv[1], kv[1], s[r]);
+                        s[r] = fmaf(qv[2], kv[2], s[r]); s[r] = fmaf(qv[3], kv[3], s[r]);
+                    }
+                }
+            }
+#pragma unroll
+            for (int r = 0; r < ENC_RQ; ++r) S[r * ENC_KTP + tid] = tid < nk ? s[r] * scale : -INFINITY;
+        }
+        __syncthreads();
+        // ---- running maximum and sum; the tile's scores become its unnormalised probabilities
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            float* row = S + (4 * wave + i) * ENC_KTP;
+            float sv[ENC_KT / 64];
+            float mt = -INFINITY;
+#pragma unroll
+            for (int j = 0; j < ENC_KT / 64; ++j) { sv[j] = row[lane + 64 * j]; mt = fmaxf(mt, sv[j]); }
+            const float m_new = fmaxf(m_run[i], wave_max(mt));
+            const float alpha = m_run[i] == -INFINITY ? 0.f : expf(m_run[i] - m_new);
+            const float m_sub = m_new == -INFINITY ? 0.f : m_new;          // every score so far is -inf (the caller's own): the tile's terms are zeros
+            float sum = 0.f;
+#pragma unroll
+            for (int j = 0; j < ENC_KT / 64; ++j) { const float e = expf(sv[j] - m_sub); row[lane + 64 * j] = e; sum += e; }
+            l_run[i] = l_run[i] * alpha + wave_sum(sum);
+            m_run[i] = m_new;
+            if (lane == 0) alpha_s[4 * wave + i] = alpha;
+        }
+        __syncthreads();
+        // ---- acc = acc alpha + P V of this tile
+        if (g < NG) {
+            float part[RPG][4];
+#pragma unroll
+            for (int r = 0; r < RPG; ++r)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) part[r][e] = 0.f;
+            const float* vp = V + (size_t)k0 * ldv + head * D + c;
+            int j = 0;
+            for (; j + 3 < nk; j += 4) {
+                float v[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = vp[(size_t)(j + e) * ldv];
+#pragma unroll
+                for (int r = 0; r < RPG; ++r) {
+                    const int row = g * RPG + r;
+                    if (row < ENC_RQ) {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) part[r][e] = fmaf(S[row * ENC_KTP + j + e], v[e], part[r][e]);
+                    }
+                }
+            }
+            for (; j < nk; ++j) {
+                const float v = vp[(size_t)j * ldv];
+#pragma unroll
+                for (int r = 0; r < RPG; ++r) {
+                    const int row = g * RPG + r;
+                    if (row < ENC_RQ) part[r][0] = fmaf(S[row * ENC_KTP + j], v, part[r][0]);
+                }
+            }
+#pragma unroll
+            for (int r = 0; r < RPG; ++r) {
+                const int row = g * RPG + r;
+                if (row < ENC_RQ) acc[r] = acc[r] * alpha_s[row] + ((part[r][0] + part[r][1]) + (part[r][2] + part[r][3]));
+            }
+        }
+        __syncthreads();
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) l_s[4 * wave + i] = l_run[i];
+    }
+    __syncthreads();
+    if (g < NG) {
+#pragma unroll
+        for (int r = 0; r < RPG; ++r) {
+            const int row = g * RPG + r;
+            if (row < nq) O[(size_t)(q0 + row) * ldo + head * D + c] = acc[r] / l_s[row];
+        }
+    }
+}
+
+svi_status launch_enc_attention_stream(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo, int Lq, int Lk,
+                                       int heads, int D, float scale, hipStream_t st) {
+    SVI_REQUIRE(Lq > 0 && Lk > 0 && heads > 0 && heads <= 65535, "streaming encoder attention: %d queries, %d keys, %d heads", Lq, Lk, heads);
+    dim3 grid((Lq + ENC_RQ - 1) / ENC_RQ, heads), block(256);
+#define ENC_CASE(DD)                                                                                                                        \
+    case DD:                                                                                                                                \
+        hipLaunchKernelGGL((enc_attention_stream_kernel<DD>), grid, block, 0, st, Q, ldq, K, ldk, V, ldv, O, ldo, Lq, Lk, scale);             \
+        break;
+    switch (D) {
+        ENC_CASE(32) ENC_CASE(64) ENC_CASE(80) ENC_CASE(128)
+        default: svi_set_error("streaming encoder attention: head dim %d (supported: 32, 64, 80, 128)", D); return SVI_ERR_UNSUPPORTED;
+    }
+#undef ENC_CASE
+    SVI_LAUNCH_CHECK();
+    return SVI_OK;
+}
+
+// the fp32 pieces of svi_encoders.hip, by the names this file calls them.  Attention: the resident kernel (whole score rows in LDS) up to its 2048
+// keys — the same launch and the same bits as before there was a choice — and the streaming kernel above.
 svi_status svi_launch_enc_attention_f32(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo, int Lq, int Lk,
                                         int heads, int D, float scale, hipStream_t st) {
+    if (Lk > W2V_MAX_FRAMES) return launch_enc_attention_stream(Q, ldq, K, ldk, V, ldv, O, ldo, Lq, Lk, heads, D, scale, st);
     return launch_enc_attention<float, false>(Q, ldq, K, ldk, V, ldv, O, ldo, Lq, Lk, heads, D, scale, nullptr, nullptr, 0, st);
 }
 svi_status svi_launch_layernorm_f32(const float* x, float* out, const float* w, const float* b, int rows, int dim, float eps, hipStream_t st) {
@@ -220,6 +380,7 @@ struct svi_w2v {
     svi_w2v_config cfg{};
     std::map<std::string, Param> w;
     char* ws = nullptr; size_t ws_bytes = 0;
+    int max_frames = W2V_MAX_FRAMES;                 // svi_w2v_set_max_frames
 };
 
 namespace {
@@ -293,12 +454,20 @@ svi_status w2v_check_request(svi_w2v* h, const void* samples, int64_t n_samples,
     SVI_REQUIRE(h && samples, "%s: null argument", who);
     SVI_REQUIRE(n_samples >= 1, "%s: %lld samples (need at least 1)", who, (long long)n_samples);
     SVI_REQUIRE(seq_len >= 1, "%s: seq_len %d (need at least 1: 1/25 s of audio)", who, seq_len);
-    SVI_REQUIRE(seq_len <= W2V_MAX_FRAMES,
-                "%s: seq_len %d is above the encoder attention's limit of 2048 keys (about 81 s of audio at 25 frames per second); "
-                "encode the audio in pieces", who, seq_len);
+    if (h->max_frames == W2V_MAX_FRAMES)
+        SVI_REQUIRE(seq_len <= W2V_MAX_FRAMES,
+                    "%s: seq_len %d is above the encoder attention's limit of 2048 keys (about 81 s of audio at 25 frames per second); "
+                    "encode the audio in pieces, or raise this handle's limit with svi_w2v_set_max_frames (up to %d)", who, seq_len, W2V_FRAME_CAP);
+    SVI_REQUIRE(seq_len <= h->max_frames, "%s: seq_len %d is above this handle's limit of %d frames (svi_w2v_set_max_frames, up to %d)", who, seq_len,
+                h->max_frames, W2V_FRAME_CAP);
     SVI_REQUIRE(n_samples <= 0x7fffffffLL, "%s: %lld samples (limit 2^31 - 1)", who, (long long)n_samples);
     SVI_REQUIRE(w2v_frames_after((long)n_samples, W2V_CONVS) >= 1, "%s: %lld samples are shorter than the convolution stack's receptive field (400 samples)",
                 who, (long long)n_samples);
+    // the largest launches with one thread per value: the first layer's GroupNorm over [frames_1, conv_dim], the feed-forward's GELU over [seq_len, ffn]
+    const long t1 = w2v_frames_after((long)n_samples, 1), wide = std::max(std::max(h->cfg.conv_dim, h->cfg.hidden), h->cfg.ffn);
+    SVI_REQUIRE(t1 * h->cfg.conv_dim <= W2V_LAUNCH_ELEMS, "%s: %lld samples are %ld rows of %d channels after the first convolution layer (limit 2^32 - 256 values)",
+                who, (long long)n_samples, t1, h->cfg.conv_dim);
+    SVI_REQUIRE((long)seq_len * wide <= W2V_LAUNCH_ELEMS, "%s: seq_len %d of %ld channels (limit 2^32 - 256 values)", who, seq_len, wide);
     SVI_TRY(svi_w2v_check_bound(h));
     return SVI_OK;
 }
@@ -491,6 +660,34 @@ extern "C" svi_status svi_w2v_check_bound(svi_w2v* h) {
     for (const auto& k : w2v_keys(h->cfg))
         if (!h->w.count(k)) { svi_set_error("audio encoder parameter '%s' was never bound", k.c_str()); return SVI_ERR_UNBOUND; }
     return SVI_OK;
+}
+
+extern "C" svi_status svi_w2v_set_max_frames(svi_w2v* h, int32_t max_frames) {
+    SVI_REQUIRE(h, "svi_w2v_set_max_frames: null handle");
+    SVI_REQUIRE(max_frames >= 1 && max_frames <= W2V_FRAME_CAP, "svi_w2v_set_max_frames: max_frames %d (1 .. %d)", max_frames, W2V_FRAME_CAP);
+    h->max_frames = max_frames;
+    return SVI_OK;
+}
+
+extern "C" svi_status svi_encoder_attention_f32(const float* Q, int32_t ldq, const float* K, int32_t ldk, const float* V, int32_t ldv, float* O, int32_t ldo,
+                                                int32_t Lq, int32_t Lk, int32_t heads, int32_t D, float scale, int32_t kernel, svi_stream stream) {
+    SVI_REQUIRE(Q && K && V && O, "svi_encoder_attention_f32: null argument");
+    SVI_REQUIRE(D == 32 || D == 64 || D == 80 || D == 128, "svi_encoder_attention_f32: D %d (the encoder attention has 32, 64, 80, 128)", D);
+    SVI_REQUIRE(heads >= 1 && heads <= 65535 && Lq >= 1 && Lk >= 1, "svi_encoder_attention_f32: heads %d (1 .. 65535), Lq %d, Lk %d (at least 1)", heads, Lq, Lk);
+    SVI_REQUIRE(Lq <= W2V_FRAME_CAP, "svi_encoder_attention_f32: Lq %d is above the cap of %d rows", Lq, W2V_FRAME_CAP);
+    SVI_REQUIRE(Lk <= W2V_FRAME_CAP, "svi_encoder_attention_f32: Lk %d is above the cap of %d keys", Lk, W2V_FRAME_CAP);
+    const long row = (long)heads * D;
+    SVI_REQUIRE(ldq >= row, "svi_encoder_attention_f32: ldq %d is smaller than heads * D = %ld", ldq, row);
+    SVI_REQUIRE(ldk >= row, "svi_encoder_attention_f32: ldk %d is smaller than heads * D = %ld", ldk, row);
+    SVI_REQUIRE(ldv >= row, "svi_encoder_attention_f32: ldv %d is smaller than heads * D = %ld", ldv, row);
+    SVI_REQUIRE(ldo >= row, "svi_encoder_attention_f32: ldo %d is smaller than heads * D = %ld", ldo, row);
+    SVI_REQUIRE((((uintptr_t)Q | (uintptr_t)K | (uintptr_t)V | (uintptr_t)O) & 3) == 0, "svi_encoder_attention_f32: operands must be 4-byte aligned");
+    SVI_REQUIRE(kernel >= 0 && kernel <= 2, "svi_encoder_attention_f32: kernel %d (0: as the audio encoder launches, 1: resident, 2: streaming)", kernel);
+    SVI_REQUIRE(kernel != 1 || Lk <= W2V_MAX_FRAMES, "svi_encoder_attention_f32: kernel 1 (resident) holds at most 2048 keys, Lk is %d", Lk);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (kernel == 2) return launch_enc_attention_stream(Q, ldq, K, ldk, V, ldv, O, ldo, Lq, Lk, heads, D, scale, st);
+    if (kernel == 1) return launch_enc_attention<float, false>(Q, ldq, K, ldk, V, ldv, O, ldo, Lq, Lk, heads, D, scale, nullptr, nullptr, 0, st);
+    return svi_launch_enc_attention_f32(Q, ldq, K, ldk, V, ldv, O, ldo, Lq, Lk, heads, D, scale, st);
 }
 
 extern "C" svi_status svi_w2v_frames(int64_t n_samples, int64_t* out) {

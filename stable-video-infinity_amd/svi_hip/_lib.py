@@ -154,6 +154,8 @@ SYMBOLS = [
     ("svi_w2v_frames", _i32, [_i64, C.POINTER(_i64)]),
     ("svi_w2v_forward", _i32, [_vp, _vp, _i64, _i32, _vp, _i32, _vp]),
     ("svi_w2v_forward_stage", _i32, [_vp, _vp, _i64, _i32, _i32, _vp, _i64, _vp]),
+    ("svi_w2v_set_max_frames", _i32, [_vp, _i32]),
+    ("svi_encoder_attention_f32", _i32, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _vp]),
 ]
 
 _lib = None

@@ -123,9 +123,10 @@ def load_image_encoder(path: str, device="cuda"):
     return WanImageEncoder.from_state_dict(_load_any(path, device), device=device, num_heads=16)
 
 
-def load_audio_encoder(path: str, device="cuda"):
+def load_audio_encoder(path: str, device="cuda", max_frames=None):
     """svi_hip.WanAudioEncoder from a Hugging Face wav2vec2 directory (chinese-wav2vec2-base): config.json plus model.safetensors or
-    pytorch_model.bin (a torch pickle of the state dict).  Weight-norm keys of either spelling are folded at bind time."""
+    pytorch_model.bin (a torch pickle of the state dict).  Weight-norm keys of either spelling are folded at bind time.  max_frames: the encoder's
+    per-call frame limit (None: 2048, about 81 s of audio; see WanAudioEncoder)."""
     import json
     import os
     from .encoders import WanAudioEncoder
@@ -133,5 +134,5 @@ def load_audio_encoder(path: str, device="cuda"):
         config = json.load(f)
     for name in ("model.safetensors", "pytorch_model.bin"):
         if os.path.exists(os.path.join(path, name)):
-            return WanAudioEncoder.from_state_dict(_load_any(os.path.join(path, name), device), config, device=device)
+            return WanAudioEncoder.from_state_dict(_load_any(os.path.join(path, name), device), config, device=device, max_frames=max_frames)
     raise FileNotFoundError(f"{path}: neither model.safetensors nor pytorch_model.bin")

@@ -179,6 +179,8 @@ class WanImageEncoder:
 W2V_CONV_KERNEL, W2V_CONV_STRIDE = (10, 3, 3, 3, 3, 2, 2), (5, 2, 2, 2, 2, 2, 2)
 W2V_STAGES = dict(wave=0, interp=8, proj=9, pos=10, enc_ln=11)          # conv layer i: 1 + i; block l: 12 + l (svi_w2v_forward_stage)
 _W2V_POS = "encoder.pos_conv_embed.conv."
+W2V_DEFAULT_MAX_FRAMES = 2048            # a fresh handle's frame limit: the resident encoder attention's key count, about 81 s of audio
+W2V_FRAME_CAP = 65536                    # W2V_FRAME_CAP of csrc/svi_wav2vec.hip: the most max_frames can be (43.7 min at 25 frames per second)
 
 
 def audio_frames(n_samples: int) -> int:
@@ -211,9 +213,15 @@ class WanAudioEncoder:
     """The talk variant's audio encoder on the device: wav2vec2-base as utils/audio_process.py:18-41 get_embedding runs it
     (utils/src/audio_analysis/wav2vec2.py Wav2Vec2Model.forward with seq_len and output_hidden_states=True), fp32; parameters are fp32 copies
     owned here.  The input is the ALREADY loudness-normalised 16 kHz mono array: loudness normalisation (pyloudnorm) and reading wav / mp4 files
-    stay with the caller."""
+    stay with the caller.
 
-    def __init__(self, conv_dim=512, hidden=768, ffn=3072, num_heads=12, num_layers=12, pos_kernel=128, pos_groups=16, eps=1e-5):
+    max_frames: the most frames one encode() serves.  None keeps the handle's 2048 (about 81 s at 25 frames per second: the resident attention kernel);
+    up to W2V_FRAME_CAP for longer audio — the reference encodes a file in one call, so a long file cannot be encoded in pieces.  Results of at most
+    2048 frames do not depend on it, bit for bit."""
+
+    FRAME_CAP = W2V_FRAME_CAP
+
+    def __init__(self, conv_dim=512, hidden=768, ffn=3072, num_heads=12, num_layers=12, pos_kernel=128, pos_groups=16, eps=1e-5, max_frames=None):
         self.conv_dim, self.hidden, self.ffn, self.num_heads, self.num_layers = conv_dim, hidden, ffn, num_heads, num_layers
         self.pos_kernel, self.pos_groups, self.eps = pos_kernel, pos_groups, eps
         cfg = L.W2vConfig(conv_dim, hidden, ffn, num_heads, num_layers, pos_kernel, pos_groups, eps)
@@ -221,6 +229,19 @@ class WanAudioEncoder:
         L.check(L.lib().svi_w2v_create(C.byref(cfg), C.byref(h)), "svi_w2v_create")
         self._h = h
         self._params: Dict[str, torch.Tensor] = {}
+        self._max_frames = W2V_DEFAULT_MAX_FRAMES
+        if max_frames is not None:
+            self.max_frames = max_frames
+
+    @property
+    def max_frames(self) -> int:
+        """The most frames (seq_len) one encode() or stage() call serves."""
+        return self._max_frames
+
+    @max_frames.setter
+    def max_frames(self, value: int) -> None:
+        L.check(L.lib().svi_w2v_set_max_frames(self._h, int(value)), "svi_w2v_set_max_frames")
+        self._max_frames = int(value)
 
     @staticmethod
     def config_from(config) -> dict:
@@ -239,7 +260,7 @@ class WanAudioEncoder:
                     pos_groups=get("num_conv_pos_embedding_groups", 16), eps=get("layer_norm_eps", 1e-5))
 
     @classmethod
-    def from_state_dict(cls, state_dict: Dict[str, torch.Tensor], config, device="cuda") -> "WanAudioEncoder":
+    def from_state_dict(cls, state_dict: Dict[str, torch.Tensor], config, device="cuda", max_frames=None) -> "WanAudioEncoder":
         """state_dict: Wav2Vec2Model's keys (a "wav2vec2." prefix of a task head's checkpoint is stripped, its other keys are skipped); config: a
         Wav2Vec2Config or the dict of config.json.  The positional convolution's weight norm is folded here (fold_weight_norm)."""
         sd = {}
@@ -248,14 +269,14 @@ class WanAudioEncoder:
                 k = k[len("wav2vec2."):]
             if k.startswith(("feature_extractor.", "feature_projection.", "encoder.")):
                 sd[k] = v
-        m = cls(**cls.config_from(config))
+        m = cls(**cls.config_from(config), max_frames=max_frames)
         m.bind({k: v.to(device=device, dtype=torch.float32).contiguous() for k, v in fold_weight_norm(sd).items()})
         return m
 
     @classmethod
-    def from_module(cls, hf_model, device="cuda") -> "WanAudioEncoder":
+    def from_module(cls, hf_model, device="cuda", max_frames=None) -> "WanAudioEncoder":
         """An existing (reference) Wav2Vec2Model: its parameters are copied to fp32 tensors on the device."""
-        return cls.from_state_dict(dict(hf_model.state_dict()), hf_model.config, device=device)
+        return cls.from_state_dict(dict(hf_model.state_dict()), hf_model.config, device=device, max_frames=max_frames)
 
     def bind(self, state_dict: Dict[str, torch.Tensor]) -> None:
         _bind_all(L.lib().svi_w2v_bind_weight, self._h, state_dict, torch.float32, L.SVI_F32, self._params, "audio encoder")

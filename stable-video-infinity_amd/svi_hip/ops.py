@@ -192,6 +192,40 @@ def audio_windows(emb: torch.Tensor, start: int, T_latent: int):
     return first, latter
 
 
+ENCODER_ATTENTION_KERNELS = {"auto": 0, "resident": 1, "streaming": 2}
+ENCODER_ATTENTION_RESIDENT_KEYS = 2048      # the resident kernel's key count (whole score rows in LDS)
+ENCODER_ATTENTION_KEY_TILE = 256            # ENC_KT of csrc/svi_wav2vec.hip: keys per tile of the streaming kernel
+ENCODER_ATTENTION_MAX_KEYS = 65536          # W2V_FRAME_CAP of csrc/svi_wav2vec.hip: what svi_w2v_set_max_frames grants at most
+
+
+def encoder_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: Optional[float] = None, kernel=0,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The audio encoder's attention as an operator (svi_encoder_attention_f32): O = softmax(scale q k^T) v per head, fp32 throughout.
+    q [Lq, heads, D], k and v [Lk, heads, D], fp32 on the GPU, D in 32, 64, 80, 128; the last two dimensions contiguous, the row stride free (views
+    into a [L, 3 heads D] q | k | v buffer are read in place).  scale=None: 1 / sqrt(D).  kernel 0 / "auto": what the audio encoder launches (resident up
+    to 2048 keys, streaming above); 1 / "resident": whole score rows in LDS, at most 2048 keys; 2 / "streaming": key tiles of ENCODER_ATTENTION_KEY_TILE,
+    running maximum and sum, any key count up to ENCODER_ATTENTION_MAX_KEYS.  out: an fp32 [Lq, heads, D] tensor or view of the same kind to write."""
+    for t, n in ((q, "q"), (k, "k"), (v, "v")) + (((out, "out"),) if out is not None else ()):
+        if not t.is_cuda:
+            raise RuntimeError(f"{n} must live on the GPU (svi_hip has no CPU path)")
+        if t.dtype != torch.float32:
+            raise TypeError(f"{n} must be torch.float32, got {t.dtype}")
+        if t.dim() != 3 or t.shape[0] < 1 or t.stride(2) != 1 or t.stride(1) != t.shape[2]:
+            raise ValueError(f"{n} must be a non-empty [rows, heads, D] tensor whose last two dimensions are contiguous (got {tuple(t.shape)}, strides {t.stride()})")
+    Lq, heads, D = q.shape
+    if tuple(k.shape[1:]) != (heads, D) or tuple(v.shape) != tuple(k.shape):
+        raise ValueError(f"k and v must be [Lk, {heads}, {D}] (got {tuple(k.shape)} and {tuple(v.shape)})")
+    if out is None:
+        out = torch.empty((Lq, heads, D), dtype=torch.float32, device=q.device)
+    elif tuple(out.shape) != (Lq, heads, D):
+        raise ValueError(f"out must be [{Lq}, {heads}, {D}] (got {tuple(out.shape)})")
+    code = ENCODER_ATTENTION_KERNELS[kernel] if isinstance(kernel, str) else int(kernel)
+    ld = lambda t: t.stride(0) if t.shape[0] > 1 else max(t.stride(0), heads * D)      # noqa: E731  (a single row has no stride to speak of)
+    L.check(L.lib().svi_encoder_attention_f32(L.ptr(q), ld(q), L.ptr(k), ld(k), L.ptr(v), ld(v), L.ptr(out), ld(out), Lq, k.shape[0], heads, D,
+                                              float(D) ** -0.5 if scale is None else float(scale), code, L.current_stream()), "encoder_attention")
+    return out
+
+
 def pose_window(pose_u8: torch.Tensor, k: int, num_frames: int, num_motion_frames: int, height: int, width: int,
                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The dance variant's clip pose window, cut on the device (svi_pose_window): pose_u8 uint8 [N, h, w, 3], the whole pose video as the video reader

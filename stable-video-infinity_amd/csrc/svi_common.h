@@ -153,7 +153,10 @@ __device__ __forceinline__ void mx8_quant8(const float (&v)[8], bool live, int r
     for (int h2 = 0; h2 < 2; ++h2) {
         float a[4];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) a[e] = fminf(fmaxf(v[4 * h2 + e] * inv, -448.f), 448.f);      // saturate to the e4m3 range, then round to nearest even
+        for (int e = 0; e < 4; ++e) {      // saturate to the e4m3 range, then round to nearest even; a NaN goes through unclamped (fmaxf(NaN, -448) is -448) and leaves as 0x7F
+            const float t = v[4 * h2 + e] * inv;
+            a[e] = t != t ? t : fminf(fmaxf(t, -448.f), 448.f);
+        }
         unsigned pk = 0;
         pk = __builtin_amdgcn_cvt_pk_fp8_f32(a[0], a[1], pk, false);
         pk = __builtin_amdgcn_cvt_pk_fp8_f32(a[2], a[3], pk, true);

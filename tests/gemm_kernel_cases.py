@@ -374,12 +374,13 @@ def _act32(epi, y):
     return y
 
 
-def emulate_arrays(case, a, w, bias, gate, res, mutate=None):
+def emulate_arrays(case, a, w, bias, gate, res, mutate=None, acc=None):
     """The launch in fp32 on the logical operands: dict(out [M, N] bf16 values in fp32, y1, raw = before the last rounding).  `mutate` plants one of
-    the faults the host test must catch: "bias_transposed", "gate_after_res", "no_y1_rounding", "swap_columns"."""
+    the faults the host test must catch: "bias_transposed", "gate_after_res", "no_y1_rounding", "swap_columns".  `acc`: the fp32 accumulators of
+    another kernel's loop (tests/mx8_kernel_cases.py: the MX-fp8 kernels end in the same epilogue) in place of accumulate32(a, w)."""
     M, N = case["M"], case["N"]
     f32 = lambda v: None if v is None else np.asarray(v, dtype=np.float32)
-    acc = accumulate32(a, w)
+    acc = accumulate32(a, w) if acc is None else acc
     b = np.float32(0)
     if bias is not None:
         along_m = (case["bias"] == "m") != (mutate == "bias_transposed")

@@ -7,6 +7,7 @@ untouched, so the FP8 mode is a script beside it that wraps its two model builde
 
 --fp8_resident (or SVI_FP8_RESIDENT=1 in the environment): the blocks' Linear weights stay the stored e4m3 bytes — no bf16 copies; the GEMMs widen them on the way into the
 matrix pipe (WanDiT.bind(fp8_resident=True)): the same video bit for bit, one byte per parameter resident.  The bound bytes are printed either way.
+With SVI_GEMM_W8_256=1 beside it (opt-in) the large projections run on the 256-row tile that reads the stored bytes instead of the 128² tile: the same bits, faster at 14B sizes.
 
     python examples/svi_fp8_hip.py --synthetic --synthetic_model tiny-i2v --num_clips 3 --num_steps 4
     python examples/svi_fp8_hip.py --synthetic --synthetic_model tiny-i2v --num_clips 3 --num_steps 4 --fp8_resident

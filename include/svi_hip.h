@@ -78,7 +78,7 @@ int32_t svi_abi_version(void);
 /* Number of visible HIP devices (0 => every compute entry point will fail with SVI_ERR_HIP). */
 int32_t svi_device_count(void);
 
-/* A/B tooling: the library reads its environment switches (SVI_FLASH_KERNEL, SVI_FLASH_TWO_PASS, SVI_FLASH_M16, SVI_FLASH_SPLIT, SVI_GEMM_KERNEL, SVI_GEMM_GM, SVI_GEMM_PF,
+/* A/B tooling: the library reads its environment switches (SVI_FLASH_KERNEL, SVI_FLASH_TWO_PASS, SVI_FLASH_M16, SVI_FLASH_SPLIT, SVI_GEMM_KERNEL, SVI_GEMM_GM, SVI_GEMM_PF, SVI_GEMM_W8_256,
  * SVI_CROSS_DEDUP, SVI_CROSS_FUSED, SVI_RMS_ROWS, SVI_QK_FUSED, SVI_MX8_FUSED, SVI_QK8_FUSED, SVI_VAE_EXACT_FP32, SVI_VAE_X2H, SVI_VAE_DMA, SVI_VAE_UP_PHASES, SVI_VAE_TILE_ORDER, SVI_VAE_PAIR, SVI_T5_BUCKETS — all of them select between kernels that
  * compute the same result, bit for bit or within the stated parity bounds — and SVI_WS_LIMIT_MB, a budget in MiB beyond which a DiT workspace is refused with
  * SVI_ERR_OOM as if the allocation had failed (callers that share the device; the stacked CFG pair then falls back to its unstacked form, same bits);
@@ -374,7 +374,8 @@ svi_status svi_attention_last_flagged(svi_stream stream, int32_t* flagged_out, i
  * the items of a partly filled last round are cut along the key axis (csrc/svi_attention.hip flash_splits). */
 svi_status svi_gemm_plan(int32_t M, int32_t N, int32_t K, int32_t epilogue, int32_t skinny, int32_t compute_units, int32_t* kernel_out);
 /* svi_gemm_w8_plan: the kernel svi_gemm_bf16_w8 takes for the same problem — svi_gemm_plan's answer where that kernel has an e4m3-weight form (0 and 128);
- * the LDS-DMA fed tiles (192 / 259 / 260) have none and map to 128. */
+ * the LDS-DMA fed tiles (192 / 259 / 260) map to 128.  With SVI_GEMM_W8_256=1 (opt-in) those three map to 260 instead, the two-phase 256^2 tile reading
+ * the stored bytes (the 192-wide and the four-phase schedule have no e4m3 twin); everything else answers as without the switch. */
 svi_status svi_gemm_w8_plan(int32_t M, int32_t N, int32_t K, int32_t epilogue, int32_t skinny, int32_t compute_units, int32_t* kernel_out);
 svi_status svi_attention_plan(int32_t s_q, int32_t s_kv, int32_t heads, int32_t compute_units, int32_t* out4);
 /* ABI v11 — the VAE's plane-fed residual-block convolution (3x3x3 over Cin -> Cout, stride 1, causal, 'same'; input [frames][Ho][Wo][Cin]):

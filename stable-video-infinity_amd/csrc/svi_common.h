@@ -62,6 +62,8 @@ struct SviSwitches {
     int gemm_kernel = 0;         // SVI_GEMM_KERNEL = 128 | 192 | 259 | 260 : force the 128^2 kernel / the 256 x 192 tile / the 256^2 tile with four / two phases per K tile (0: by tile count)
     int gemm_pf = 0;             // SVI_GEMM_PF = 1 | 4 | 8 : the 128^2 kernel's loop — 1 = one K tile of loads in flight, 4 = four, 8 = four on eight waves (0: 8 when the launch is at most one workgroup per CU, else 1)
     int gemm_gm = 0;             // SVI_GEMM_GM = n >= 1 : row panels per tile group (0: per shape)
+    int gemm_w8_256 = 0;         // SVI_GEMM_W8_256 = 1 : (opt-in) GEMMs with W stored as e4m3 (FP8-resident weights) that the bf16 planner gives to a 256-row tile run the
+                                 // two-phase 256^2 loop on the stored bytes (gemm_w8_nt_256e_kernel, plan id 260) instead of the 128^2 tile (bit-identical)
     int vae_exact_fp32 = 0;      // SVI_VAE_EXACT_FP32 : fp32-MFMA convolution everywhere
     int vae_no_x2h = 0;          // SVI_VAE_X2H = 0 : the three-term bf16 convolution also where the two-term fp16 form applies (same parity bounds)
     int vae_dma = 1;             // SVI_VAE_DMA = 0 : residual-block convolutions split their fp32 input on the fly (conv_igemm_x3_kernel<true>) instead of reading
@@ -233,7 +235,7 @@ svi_status svi_launch_gemm(const SviGemmArgs& g, hipStream_t st);
 int svi_gemm_choose(const SviGemmArgs& g, int compute_units);          // which kernel svi_launch_gemm takes (pure; see svi_gemm.hip)
 // FP8-resident weights: the same GEMM with ONE operand stored as OCP e4m3 bytes and widened (exactly) on its way into the matrix pipe — e8 = 1: g.W (and g.W2)
 // [N, ldw bytes]; e8 = 2: g.A [M, lda bytes] (the transposed value projection: the stored weight is the A operand).  The leading dimension of the e4m3 operand
-// is in bytes, a multiple of 16.  Per element the bits of svi_launch_gemm on the widened copy, run on the kernel svi_gemm_choose_e8 names (0 or 128).
+// is in bytes, a multiple of 16.  Per element the bits of svi_launch_gemm on the widened copy, run on the kernel svi_gemm_choose_e8 names (0 or 128; 260 under SVI_GEMM_W8_256 = 1).
 svi_status svi_launch_gemm_e8(const SviGemmArgs& g, int e8, hipStream_t st);
 int svi_gemm_choose_e8(const SviGemmArgs& g, int compute_units, int e8);
 // how svi_launch_flash splits a launch into work items (pure; see svi_attention.hip): items [0, whole) run whole, the rest in `pieces` workgroups each

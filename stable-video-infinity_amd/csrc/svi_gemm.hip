@@ -1054,6 +1054,192 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_256e_kernel(SviGemmArgs g
 }
 
 // =================================================================================================
+// gemm_bf16_nt_256e_kernel<2, 256> with W stored as OCP e4m3 bytes [N, ldw bytes] (FP8-resident weights; plan id 260 of svi_gemm_choose_e8 under
+// SVI_GEMM_W8_256 = 1).  A kernel of its own, not a mode of the template above: routing both dtypes through one body moved the bf16 instantiations'
+// register allocation (DESIGN.md, FP8-resident weights).  Same output tile, wave grid, MFMA, k order per accumulator element, epilogue and tile order —
+// and e4m3 -> bf16 is exact — so the bits of the bf16 kernel on the widened copy.
+//
+// What differs is the W side of a K tile.  Its LDS image is the stored bytes, [256 rows][64 B] = 16 KiB at the W offset of the K-tile buffer (the
+// upper 16 KiB of the bf16 image's W region stay unused; the buffer flip is the same XOR).  LDS-DMA moves 16 B per lane, so a wave instruction covers
+// 16 rows x 64 B and the eight waves 128 rows: TWO W pieces per wave and K tile (piece j: rows 128 j + 16 wave + lane / 4) against four for bf16.
+// Lane l's fragment of k-step kk (row l & 15, k = 32 kk + 8 (l >> 4) .. + 7) is ONE 8-byte read, 8-byte aligned, at byte 32 kk + 8 (l >> 4) of its
+// row = half (l >> 4) & 1 of 16-byte chunk 2 kk + (l >> 5).  It is widened in registers (v_cvt_scalef32_pk_bf16_fp8 at scale 1.0, e4m3x8_to_bf16x8)
+// in the L section of phase 0, in front of the two clusters that consume it: 8 fragments x 4 conversions = 32 VALU instructions per wave and K tile,
+// issued while the SIMD's other wave is inside its MFMA cluster.  (Staging W through registers — global load, widen, ds_write, as the 128^2 form
+// does — was not built: it keeps the bf16 image's 32 KiB of W per K tile in LDS and adds a ds_write pass and staging VGPRs to a loop whose bf16 form sits at 255.)
+// Bank swizzle (on the SOURCE chunk, as above: the DMA writes lane-linear): LDS slot (row r, position p) holds 16-byte chunk p ^ ((r >> 2) & 3) of
+// row r's 64 bytes.  ds_read_b64 conflicts are counted per 32-lane half on banks (a / 4) % 64, a 256-byte bank row = four 64-byte rows: a half is
+// 16 rows x halves {0, 1} of ONE chunk c; the four rows that share r & 3 (the same 64 bytes of the bank row) differ in r >> 2 and so sit at four
+// different positions c ^ (r >> 2) — 4 (r & 3) x 4 positions x 2 halves = 32 distinct 8-byte slots = the whole bank row: 0 conflicts expected.
+// A wave's DMA instruction reads whole 64-byte rows (the permutation stays inside them).
+// Hand-off: the rules of the section header above, unchanged — a wave waits for its OWN fragment reads (lgkmcnt(0)) before the barrier that ends its
+// L section; a staged buffer is first read one phase after the counted vmcnt that retires this wave's shares of it; raw s_barrier only in the loop.
+// Row OOB: the W descriptor is sized in bytes, (N - 1) ldw + K; rows past N read zeros.  launch_gemm keeps N ldw below 2^31 bytes (fits32).
+// =================================================================================================
+__device__ __forceinline__ int lds_w8_off(int row, int chunk) {   // byte offset inside a [256][64] e4m3 tile
+    return row * 64 + ((chunk ^ ((row >> 2) & 3)) << 4);
+}
+// (volatile: each fragment stays ONE ds_read_b64.  Left to itself the compiler pairs them into ds_read2st64_b64, which banks on (a / 4) % 32 and moves half
+// the bytes per LDS cycle — the swizzle above is counted for ds_read_b64.)
+typedef const volatile __attribute__((address_space(3))) u32x2* lds_u32x2_t;
+
+__global__ __launch_bounds__(512, 2) void gemm_w8_nt_256e_kernel(SviGemmArgs g, int tiles_m, int tiles_n, int GM) {
+    constexpr int MI = 4, NI = 2, MH = 2;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int lds0 = (int)(size_t)(lptr_t)smem;
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int grp = wave >> 2;
+    const int wm = wave >> 2, wn = wave & 3;
+    const int l31 = lane & 31, hi = lane >> 5;
+
+    const int nwg = tiles_m * tiles_n;
+    const int orig = blockIdx.x;
+    const int xcd = orig & 7, q = nwg >> 3, rr = nwg & 7;
+    const int swz = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (orig >> 3);
+    const int group = swz / (GM * tiles_n);
+    const int first_m = group * GM;
+    const int gm = min(GM, tiles_m - first_m);
+    const int in_group = swz - group * GM * tiles_n;
+    const int tile_n = in_group / gm;
+    const int tile_m = first_m + (in_group - tile_n * gm);
+    const int m0 = tile_m * TM, n0 = tile_n * TN;
+    const unsigned char* W8 = reinterpret_cast<const unsigned char*>(g.W);
+    if (g.W2 && n0 >= g.n_split) {                          // q | k side by side: the base moves back by n_split rows of ldw BYTES
+        W8 = reinterpret_cast<const unsigned char*>(g.W2) - (size_t)g.n_split * g.ldw;
+        g.bias = g.bias2 ? g.bias2 - g.n_split : nullptr;
+    }
+    const __amdgpu_buffer_rsrc_t rs_a = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(g.A), 0, (int)(((unsigned)(g.M - 1) * (unsigned)g.lda + (unsigned)g.K) * 2u), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(W8), 0, (int)((unsigned)(g.N - 1) * (unsigned)g.ldw + (unsigned)g.K), 0x00020000);
+    // A: a wave's DMA instruction covers 8 rows x 128 B, piece j holds rows 64 j + 8 wave + lane / 8 (as in the bf16 kernel).
+    // W: 16 rows x 64 B, piece j holds rows 128 j + 16 wave + lane / 4; (128 j does not reach the swizzle's row bits 2..3).
+    const int r8 = wave * 8 + (lane >> 3);
+    const int c8 = (lane & 7) ^ ((r8 >> 1) & 7);
+    const int r16 = wave * 16 + (lane >> 2);
+    const int c4 = (lane & 3) ^ ((r16 >> 2) & 3);
+    const int a_vo = (r8 * g.lda + c8 * 8) * 2, w_vo = r16 * g.ldw + c4 * 16;
+    const unsigned a_so0 = (unsigned)m0 * (unsigned)g.lda * 2u, w_so0 = (unsigned)n0 * (unsigned)g.ldw;
+    const unsigned a_j = 64u * (unsigned)g.lda * 2u, w_j = 128u * (unsigned)g.ldw;
+    const int nk = g.K / BK;
+    auto stage_a = [&](int kt, int b) {                     // the A tile of K tile kt -> buffer b: four pieces per wave
+        const unsigned so = a_so0 + (unsigned)kt * (BK * 2);
+        char* dst = smem + b * E_BUF + wave * 1024;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_a, (lptr_t)(dst + j * 8192), 16, a_vo, (int)(so + (unsigned)j * a_j), 0, 0);
+    };
+    auto stage_w = [&](int kt, int b) {                     // the W tile (bytes) of K tile kt -> buffer b: two pieces per wave
+        const unsigned so = w_so0 + (unsigned)kt * BK;
+        char* dst = smem + b * E_BUF + 2 * E_HALF + wave * 1024;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w, (lptr_t)(dst + j * 8192), 16, w_vo, (int)(so + (unsigned)j * w_j), 0, 0);
+    };
+
+    f32x4 acc[2 * NI][2 * MI];
+#pragma unroll
+    for (int i = 0; i < 2 * NI; ++i)
+#pragma unroll
+        for (int j = 0; j < 2 * MI; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) acc[i][j][r] = 0.f;
+
+    const int l15 = lane & 15, g4 = lane >> 4;
+    int a_addr[2], w_addr[2];          // this lane's fragment of k-step kk: 16-row block 0 of the wave's rows (A) / columns (W), buffer 0
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+        a_addr[kk] = lds0 + lds_tile_off(wm * (32 * MI) + l15, 4 * kk + g4);
+        w_addr[kk] = lds0 + 2 * E_HALF + lds_w8_off(wn * (32 * NI) + l15, 2 * kk + (g4 >> 1)) + (g4 & 1) * 8;
+    }
+    u32x4 xlo[2 * MH][2], xup[2 * MH][2], xw[2 * NI][2];
+    auto read_a = [&](u32x4 (&x)[2 * MH][2], int blk0) {
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+            for (int i = 0; i < 2 * MH; ++i) x[i][kk] = *(lds_u32x4_t)(a_addr[kk] + (2 * blk0 + i) * 16 * 128);
+    };
+    auto cluster = [&](int mb0, const u32x4 (&xa)[2 * MH][2]) {
+        __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+            for (int n = 0; n < 2 * NI; ++n)
+#pragma unroll
+                for (int i = 0; i < 2 * MH; ++i)
+                    acc[n][2 * mb0 + i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, xw[n][kk]), __builtin_bit_cast(bf16x8, xa[i][kk]), acc[n][2 * mb0 + i], 0, 0, 0);
+        __builtin_amdgcn_s_setprio(0);
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    auto flip = [&](int (&ad)[2]) {
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk) ad[kk] ^= E_BUF;
+    };
+    // one K tile.  SW: tile t+1 exists (its W is staged here, its lower A fragments are read here);  SA: tile t+2 exists (its A is staged here).
+    // vmcnt counts THIS wave's outstanding DMA pieces, oldest first: A of a tile is 4 pieces, W is 2.
+    auto ktile = [&](int t, auto swc, auto sac) {
+        constexpr bool SW = decltype(swc)::value, SA = decltype(sac)::value;
+        const int b = t & 1;
+        // ---- phase 0
+        u32x2 raw[2 * NI][2];
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+            for (int i = 0; i < 2 * NI; ++i) raw[i][kk] = *(lds_u32x2_t)(w_addr[kk] + i * 16 * 64);
+        read_a(xup, MH);
+        if constexpr (SW) stage_w(t + 1, b ^ 1);
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+            for (int i = 0; i < 2 * NI; ++i) xw[i][kk] = e4m3x8_to_bf16x8(raw[i][kk]);
+        __builtin_amdgcn_sched_barrier(0);                                       // the conversions stay in the L section, beside the other wave's MFMA cluster
+        // in flight on entry (SW): A(t+1), 4 pieces (staged in phase 1 of tile t-1, or by the prologue); the 2 W(t+1) pieces above are the newest
+        if constexpr (SW) E_WAIT("s_waitcnt vmcnt(2) lgkmcnt(0)");                // all but the 2 newest: A(t+1) has landed (this wave's shares); its W may still fly
+        else E_WAIT("s_waitcnt lgkmcnt(0)");                                     // last tile: nothing was staged, nothing is in flight
+        E_BAR();
+        cluster(0, xlo);
+        E_BAR();
+        // ---- phase 1
+        flip(a_addr); flip(w_addr);
+        if constexpr (SW) read_a(xlo, 0);
+        if constexpr (SA) {
+            stage_a(t + 2, b);
+            E_WAIT("s_waitcnt vmcnt(4) lgkmcnt(0)");                              // in flight: W(t+1) 2 pieces, then A(t+2) 4 pieces; all but the 4 newest: W(t+1) has landed
+        } else if constexpr (SW) {
+            E_WAIT("s_waitcnt vmcnt(0) lgkmcnt(0)");                              // only W(t+1) is in flight: drain it
+        }
+        E_BAR();
+        cluster(MH, xup);
+        E_BAR();
+    };
+    std::true_type YES;
+    std::false_type NO;
+
+    // prologue: tile 0 whole, the A tile of tile 1 behind it.  Issue order A(0) 4, W(0) 2, A(1) 4: all but the 4 newest = tile 0 has landed
+    stage_a(0, 0);
+    stage_w(0, 0);
+    if (nk > 1) {
+        stage_a(1, 1);
+        E_WAIT("s_waitcnt vmcnt(4)");
+    } else {
+        E_WAIT("s_waitcnt vmcnt(0)");
+    }
+    E_BAR();
+    read_a(xlo, 0);
+    if (grp == 1) E_BAR();                                 // the second wave row runs one barrier behind the first from here on
+    int t = 0;
+    for (; t + 2 < nk; ++t) ktile(t, YES, YES);
+    if (nk >= 2) { ktile(t, YES, NO); ++t; }
+    ktile(t, NO, NO);
+    if (grp == 0) E_BAR();
+#pragma unroll
+    for (int n = 0; n < 2 * NI; ++n)
+#pragma unroll
+        for (int i = 0; i < 2 * MI; ++i) asm volatile("" : "+v"(acc[n][i]));
+    asm volatile("s_nop 7\n\ts_nop 7" ::: "memory");      // MFMA result -> VALU read
+    __syncthreads();                                       // every wave is done with the operand buffers: the C tile may overwrite them
+    gemm256_epilogue<MI, NI, TN, false, 16>(g, acc, smem, m0, n0, tid, wm, wn, l31, hi);
+}
+
+// =================================================================================================
 // Round 6 experiment, measured and dropped (code at e21fc0e): the vendor library's shape for these problems, a 256 x 256 x 64 tile on FOUR waves
 // (128 x 128 per wave, one wave per SIMD), LDS-DMA fed ("w4") or fed through registers ("w4r").  Both were bit-identical and SLOWER:
 //                                   q|k|v    attn-out   ffn1     ffn2 (K = 8960)      [TFLOP/s, profiles/r6e_gemm_ab_w4.txt, r6f_gemm_ab_w4r.txt]
@@ -1442,10 +1628,14 @@ static int gemm_device_cus() {
 }
 
 // The kernel the e4m3-operand launch takes (svi_gemm_w8_plan): svi_gemm_choose's answer where that kernel has an e4m3 form — the skinny kernel (W stored as
-// e4m3 only) and the 128^2 tile; the LDS-DMA fed 256-row tiles (192 / 259 / 260) have none and run on the 128^2 tile (DESIGN.md, FP8-resident weights).
+// e4m3 only) and the 128^2 tile; the LDS-DMA fed 256-row tiles (192 / 259 / 260) run on the 128^2 tile (DESIGN.md, FP8-resident weights).  With
+// SVI_GEMM_W8_256 = 1 (opt-in) a launch with W stored as e4m3 that svi_gemm_choose gives to any of the three takes 260, gemm_w8_nt_256e_kernel; the 192-wide
+// and the four-phase schedule have no e4m3 twin, and neither has the A-operand form (e8 == 2), which stays on the 128^2 tile.
 int svi_gemm_choose_e8(const SviGemmArgs& g, int ncu, int e8) {
     const int kind = svi_gemm_choose(g, ncu);
-    return kind == 0 && e8 == 1 ? 0 : 128;
+    if (kind == 0 && e8 == 1) return 0;
+    if (e8 == 1 && svi_switches().gemm_w8_256 && (kind == 192 || kind == 259 || kind == 260)) return 260;
+    return 128;
 }
 
 // e8: 0 = both operands bf16; 1 = W (and W2) stored as e4m3 bytes, ldw in bytes; 2 = A stored as e4m3 bytes, lda in bytes (svi_launch_gemm_e8)
@@ -1509,7 +1699,11 @@ static svi_status launch_gemm(const SviGemmArgs& g, int e8, hipStream_t st) {
         // N = 8960 (35 column panels, ffn1): 5 gives 1161 vs 1139 at 2 and 1093 at 8 — a 5 x 6 block of concurrent tiles per XCD
         // needs the fewest operand panels (HBM fetch per launch at 2: 2.2 GB against 0.13 GB of operands, profiles/r1h_gemm_ffn1_pmc.txt)
         const int gm_rows = sw.gemm_gm ? sw.gemm_gm : (tn >= 16 ? 5 : 4);
-        if (kind == 192) {            // the 256 x 192 tile (sequence-parallel shards)
+        if (e8) {                     // W stored as e4m3 (svi_gemm_choose_e8 names 260 for e8 == 1 only): the two-phase 256^2 loop on the stored bytes
+            SVI_REQUIRE(e8 == 1 && kind == 260, "gemm: no 256-row kernel %d for e4m3 operand %d", kind, e8);
+            SVI_TRY(svi_ensure_lds(reinterpret_cast<const void*>(gemm_w8_nt_256e_kernel), LDS256_BYTES));
+            hipLaunchKernelGGL(gemm_w8_nt_256e_kernel, dim3(tm * tn), dim3(512), LDS256_BYTES, st, g, tm, tn, gm_rows);
+        } else if (kind == 192) {     // the 256 x 192 tile (sequence-parallel shards)
             const int tn3 = (g.N + TN3 - 1) / TN3;
             SVI_TRY(svi_ensure_lds(reinterpret_cast<const void*>(gemm_bf16_nt_256e_kernel<2, 192>), LDS256_BYTES));
             hipLaunchKernelGGL((gemm_bf16_nt_256e_kernel<2, 192>), dim3(tm * tn3), dim3(512), LDS256_BYTES, st, g, tm, tn3, sw.gemm_gm ? sw.gemm_gm : (tn3 >= 16 ? 5 : 4));

@@ -347,3 +347,18 @@ svi_status svi_launch_fp8_e4m3_to_bf16(const unsigned char* in, bf16* out, int64
 // fp32 C[M,N] = A[M,K] W[N,K]^T + bias[N] (+ res[M,N]) on the exact-fp32 MFMA kernel of the VAE (csrc/svi_vae.hip)
 svi_status svi_launch_gemm_f32(const float* A, int lda, const float* W, int ldw, const float* bias, float* C, int ldc, int M, int N, int K,
                                const float* res, int ldres, hipStream_t st);
+// ---- the encoders' shared kernels (svi_encoder_kernels.hip) ----
+// Encoder attention, one workgroup per head x 16 query rows, operands token-major with head hd at column hd * D.  D: svi_enc_head_dim_ok.
+constexpr int SVI_ENC_RESIDENT_KEYS = 2048;     // the resident kernel keeps whole score rows in LDS: its key limit; above it the fp32 attention streams
+constexpr int SVI_ENC_MAX_KEYS = 65536;         // query rows / keys the fp32 operator serves at most (and the audio encoder's frame cap)
+bool svi_enc_head_dim_ok(int D);
+// the bf16 module's rounding points (umT5), bias emb[bucket_tab[key - query + tab_zero]][head] (bf16 [buckets][heads]) or none; resident kernel only
+svi_status svi_launch_enc_attention_bf16(const bf16* Q, int ldq, const bf16* K, int ldk, const bf16* V, int ldv, bf16* O, int ldo, int Lq, int Lk, int heads,
+                                         int D, float scale, const bf16* emb, const int* bucket_tab, int tab_zero, hipStream_t st);
+// plain fp32; kernel: svi_encoder_attention_f32's argument
+enum { SVI_ENC_ATT_AUTO = 0, SVI_ENC_ATT_RESIDENT = 1, SVI_ENC_ATT_STREAM = 2 };
+svi_status svi_launch_enc_attention_f32(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo, int Lq, int Lk,
+                                        int heads, int D, float scale, int kernel, hipStream_t st);
+// nn.LayerNorm (biased variance) over rows of `dim` values, and x = GELU(x) with the exact (erf) form, fp32
+svi_status svi_launch_layernorm_f32(const float* x, float* out, const float* w, const float* b, int rows, int dim, float eps, hipStream_t st);
+svi_status svi_launch_gelu_erf_f32(float* x, long n, hipStream_t st);

@@ -10,28 +10,31 @@
 //             -> num_layers post-norm blocks: x = LN(x + attn(x)); x = LN(x + ffn(x))
 //   out[t][l][:] = the output of block l at frame t  (torch.stack(hidden_states[1:], 1) rearranged "b s d -> s b d")
 //
-// Activations are time-major [T, C].  The projections run on the exact-fp32 MFMA GEMM, attention and LayerNorm on the fp32 kernels of the image
-// encoder (svi_encoders.hip).  New here: one direct convolution kernel (a window of k rows of a time-major activation is k * Cin contiguous floats;
-// it serves the feature extractor's layers and, with groups and a symmetric pad, the positional convolution), the statistics over time of the
+// Activations are time-major [T, C].  The projections run on the exact-fp32 MFMA GEMM; attention, LayerNorm and GELU are the fp32 launchers of
+// svi_encoder_kernels.hip, the image encoder's too.  Here: one direct convolution kernel (a window of k rows of a time-major activation is k * Cin contiguous
+// floats; it serves the feature extractor's layers and, with groups and a symmetric pad, the positional convolution), the statistics over time of the
 // waveform and of the first layer's GroupNorm, the interpolation, and the writer of the [seq_len, layers, hidden] output.
-//
-// Compiled as ONE translation unit with svi_encoders.hip (included below; svi_hip/build.py lists this file in its place): the fp32 attention, LayerNorm
-// and GELU kernels this encoder launches are that file's, in its unnamed namespace, and stay there untouched — the same kernels, the same bits.
 //
 // Length: the reference hands the whole file to the model in one call (every frame attends to every other, the waveform statistics are the file's), so
 // a file cannot be encoded in pieces.  A handle serves up to max_frames frames per call: 2048 when it is made (the resident attention kernel's key
 // count, about 81 s), up to W2V_FRAME_CAP = 65536 (43.7 min) after svi_w2v_set_max_frames.  Up to 2048 frames the attention is the resident kernel,
-// above it the streaming kernel below (online softmax, fp32 throughout, LDS independent of the key count); nothing else in the forward
-// depends on the length.  svi_encoder_attention_f32 is that attention alone, as an operator.
-#include "svi_encoders.hip"
+// above it the streaming kernel (online softmax, fp32 throughout, LDS independent of the key count); nothing else in the forward depends on the length.
+#include <math.h>
+
+#include "svi_encoder_host.h"
+
+// This file's kernels are compiled with floating-point contraction allowed, as they always were: they used to follow the image encoder's preprocessing
+// kernel, which ends with this pragma, in one translation unit.  The committed fixtures are these bits.
+#pragma clang fp contract(fast)
 
 namespace {
 
 constexpr int W2V_CONVS = 7;
 const int W2V_KERNEL[W2V_CONVS] = {10, 3, 3, 3, 3, 2, 2};
 const int W2V_STRIDE[W2V_CONVS] = {5, 2, 2, 2, 2, 2, 2};
-constexpr int W2V_MAX_FRAMES = 2048;              // a fresh handle's frame limit: the resident encoder attention's key limit (svi_encoders.hip)
+constexpr int W2V_MAX_FRAMES = 2048;              // a fresh handle's frame limit: the resident encoder attention's key limit
 constexpr int W2V_FRAME_CAP = 65536;              // the most svi_w2v_set_max_frames grants (43.7 min at 25 frames per second); the audit is in DESIGN §4
+static_assert(W2V_MAX_FRAMES == SVI_ENC_RESIDENT_KEYS && W2V_FRAME_CAP == SVI_ENC_MAX_KEYS, "the frame limits are the encoder attention's key limits");
 constexpr long W2V_LAUNCH_ELEMS = 0xffffff00L;    // one thread per value, 256 per workgroup: the runtime launches at most 2^32 - 1 threads along x
 constexpr float W2V_GROUPNORM_EPS = 1e-5f;        // nn.GroupNorm's default (the model does not pass its layer_norm_eps there)
 constexpr float W2V_WAVE_EPS = 1e-7f;             // Wav2Vec2FeatureExtractor.zero_mean_unit_var_norm
@@ -205,248 +208,38 @@ __global__ void w2v_write_layer_kernel(const float* __restrict__ x, T* __restric
     out[((size_t)t * layers + layer) * dim + c] = (T)x[i];
 }
 
-// ---------------------------------------------------------------- streaming attention ----------------------------------------------
-// The encoder attention of svi_encoders.hip (enc_attention_kernel, ENC_RQ query rows per workgroup) for ANY key count, plain fp32 only — the audio
-// encoder past 2048 frames.  It lives here and not beside the resident kernel because that file is also the T5 / CLIP encoders' and stays byte for
-// byte what the committed profiles were collected on.  The key axis is walked in tiles of ENC_KT keys and a
-// query row keeps a running maximum m, a running sum l and an accumulator that is rescaled when the maximum moves (online softmax), so LDS and
-// registers do not grow with Lk.  One workgroup = one head x ENC_RQ query rows, as there.  Per tile:
-//   scores   thread <-> key: 16 dot products against the staged query rows; keys past Lk score -inf
-//   softmax  wave w owns rows 4w..4w+3: m' = max(m, tile max) (finite unless the caller's scores are -inf: a tile holds at least one key);
-//            alpha = exp(m - m'), 0 while m is still -inf (no (-inf) - (-inf)); p = exp(s - m'); l = l alpha + sum p
-//   P.V      thread <-> (row group, channel) as there: acc = acc alpha + sum_j p_j v_j, the tile's sum formed on its own in four interleaved chains
-// and O = acc / l after the last tile.  Every value is fp32; a term exp(s - m') that underflows is an exact zero and leaves acc and l as they were.
-// LDS: (16 D + 16 (ENC_KT + 1) + 48) x 4 B = 24.8 KiB at D = 128; registers: 16 score sums or 4 x RPG (<= 32) partial sums per thread.
-#define ENC_KT 256
-constexpr int ENC_KTP = ENC_KT + 1;               // row stride of the tile's scores: rows of two row groups in one wave fall on different banks
-template <int D>
-__global__ __launch_bounds__(256) void enc_attention_stream_kernel(const float* __restrict__ Q, int ldq, const float* __restrict__ K, int ldk,
-                                                                   const float* __restrict__ V, int ldv, float* __restrict__ O, int ldo, int Lq, int Lk,
-                                                                   float scale) {
-    __shared__ __attribute__((aligned(16))) float Qs[ENC_RQ * D];
-    __shared__ float S[ENC_RQ * ENC_KTP];
-    __shared__ float alpha_s[ENC_RQ], l_s[ENC_RQ];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, head = blockIdx.y, q0 = blockIdx.x * ENC_RQ;
-    const int nq = min(ENC_RQ, Lq - q0);
-    for (int i = tid; i < ENC_RQ * D; i += 256) {
-        const int r = i / D, c = i - r * D;
-        Qs[i] = r < nq ? Q[(size_t)(q0 + r) * ldq + head * D + c] : 0.f;
-    }
-    float m_run[4], l_run[4];                     // of rows 4 wave .. 4 wave + 3, the same in every lane of the wave
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { m_run[i] = -INFINITY; l_run[i] = 0.f; }
-    constexpr int NG = 256 / D, RPG = (ENC_RQ + NG - 1) / NG;
-    const int g = tid / D, c = tid - g * D;
-    float acc[RPG];
-#pragma unroll
-    for (int r = 0; r < RPG; ++r) acc[r] = 0.f;
-    __syncthreads();
-    for (int k0 = 0; k0 < Lk; k0 += ENC_KT) {
-        const int nk = min(ENC_KT, Lk - k0);
-        // ---- scores of this tile: thread <-> key
-        {
-            float s[ENC_RQ];
-#pragma unroll
-            for (int r = 0; r < ENC_RQ; ++r) s[r] = 0.f;
-            if (tid < nk) {
-                const float* kp = K + (size_t)(k0 + tid) * ldk + head * D;
-#pragma unroll 4
-                for (int cc = 0; cc < D; cc += 4) {
-                    float kv[4];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) kv[e] = kp[cc + e];
-#pragma unroll
-                    for (int r = 0; r < ENC_RQ; ++r) {
-                        const f32x4 qv = *reinterpret_cast<const f32x4*>(Qs + r * D + cc);
-                        s[r] = fmaf(qv[0], kv[0], s[r]); s[r] = fmaf(qv[1], kv[1], s[r]);
-                        s[r] = fmaf(qv[2], kv[2], s[r]); s[r] = fmaf(qv[3], kv[3], s[r]);
-                    }
-                }
-            }
-#pragma unroll
-            for (int r = 0; r < ENC_RQ; ++r) S[r * ENC_KTP + tid] = tid < nk ? s[r] * scale : -INFINITY;
-        }
-        __syncthreads();
-        // ---- running maximum and sum; the tile's scores become its unnormalised probabilities
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            float* row = S + (4 * wave + i) * ENC_KTP;
-            float sv[ENC_KT / 64];
-            float mt = -INFINITY;
-#pragma unroll
-            for (int j = 0; j < ENC_KT / 64; ++j) { sv[j] = row[lane + 64 * j]; mt = fmaxf(mt, sv[j]); }
-            const float m_new = fmaxf(m_run[i], wave_max(mt));
-            const float alpha = m_run[i] == -INFINITY ? 0.f : expf(m_run[i] - m_new);
-            const float m_sub = m_new == -INFINITY ? 0.f : m_new;          // every score so far is -inf (the caller's own): the tile's terms are zeros
-            float sum = 0.f;
-#pragma unroll
-            for (int j = 0; j < ENC_KT / 64; ++j) { const float e = expf(sv[j] - m_sub); row[lane + 64 * j] = e; sum += e; }
-            l_run[i] = l_run[i] * alpha + wave_sum(sum);
-            m_run[i] = m_new;
-            if (lane == 0) alpha_s[4 * wave + i] = alpha;
-        }
-        __syncthreads();
-        // ---- acc = acc alpha + P V of this tile
-        if (g < NG) {
-            float part[RPG][4];
-#pragma unroll
-            for (int r = 0; r < RPG; ++r)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) part[r][e] = 0.f;
-            const float* vp = V + (size_t)k0 * ldv + head * D + c;
-            int j = 0;
-            for (; j + 3 < nk; j += 4) {
-                float v[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = vp[(size_t)(j + e) * ldv];
-#pragma unroll
-                for (int r = 0; r < RPG; ++r) {
-                    const int row = g * RPG + r;
-                    if (row < ENC_RQ) {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) part[r][e] = fmaf(S[row * ENC_KTP + j + e], v[e], part[r][e]);
-                    }
-                }
-            }
-            for (; j < nk; ++j) {
-                const float v = vp[(size_t)j * ldv];
-#pragma unroll
-                for (int r = 0; r < RPG; ++r) {
-                    const int row = g * RPG + r;
-                    if (row < ENC_RQ) part[r][0] = fmaf(S[row * ENC_KTP + j], v, part[r][0]);
-                }
-            }
-#pragma unroll
-            for (int r = 0; r < RPG; ++r) {
-                const int row = g * RPG + r;
-                if (row < ENC_RQ) acc[r] = acc[r] * alpha_s[row] + ((part[r][0] + part[r][1]) + (part[r][2] + part[r][3]));
-            }
-        }
-        __syncthreads();
-    }
-    if (lane == 0) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) l_s[4 * wave + i] = l_run[i];
-    }
-    __syncthreads();
-    if (g < NG) {
-#pragma unroll
-        for (int r = 0; r < RPG; ++r) {
-            const int row = g * RPG + r;
-            if (row < nq) O[(size_t)(q0 + row) * ldo + head * D + c] = acc[r] / l_s[row];
-        }
-    }
-}
-
-svi_status launch_enc_attention_stream(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo, int Lq, int Lk,
-                                       int heads, int D, float scale, hipStream_t st) {
-    SVI_REQUIRE(Lq > 0 && Lk > 0 && heads > 0 && heads <= 65535, "streaming encoder attention: %d queries, %d keys, %d heads", Lq, Lk, heads);
-    dim3 grid((Lq + ENC_RQ - 1) / ENC_RQ, heads), block(256);
-#define ENC_CASE(DD)                                                                                                                        \
-    case DD:                                                                                                                                \
-        hipLaunchKernelGGL((enc_attention_stream_kernel<DD>), grid, block, 0, st, Q, ldq, K, ldk, V, ldv, O, ldo, Lq, Lk, scale);             \
-        break;
-    switch (D) {
-        ENC_CASE(32) ENC_CASE(64) ENC_CASE(80) ENC_CASE(128)
-        default: svi_set_error("streaming encoder attention: head dim %d (supported: 32, 64, 80, 128)", D); return SVI_ERR_UNSUPPORTED;
-    }
-#undef ENC_CASE
-    SVI_LAUNCH_CHECK();
-    return SVI_OK;
-}
-
-// the fp32 pieces of svi_encoders.hip, by the names this file calls them.  Attention: the resident kernel (whole score rows in LDS) up to its 2048
-// keys — the same launch and the same bits as before there was a choice — and the streaming kernel above.
-svi_status svi_launch_enc_attention_f32(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo, int Lq, int Lk,
-                                        int heads, int D, float scale, hipStream_t st) {
-    if (Lk > W2V_MAX_FRAMES) return launch_enc_attention_stream(Q, ldq, K, ldk, V, ldv, O, ldo, Lq, Lk, heads, D, scale, st);
-    return launch_enc_attention<float, false>(Q, ldq, K, ldk, V, ldv, O, ldo, Lq, Lk, heads, D, scale, nullptr, nullptr, 0, st);
-}
-svi_status svi_launch_layernorm_f32(const float* x, float* out, const float* w, const float* b, int rows, int dim, float eps, hipStream_t st) {
-    hipLaunchKernelGGL(layernorm_f32_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, x, out, w, b, rows, dim, eps);
-    SVI_LAUNCH_CHECK();
-    return SVI_OK;
-}
-svi_status svi_launch_gelu_erf_f32(float* x, long n, hipStream_t st) {
-    hipLaunchKernelGGL(gelu_erf_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, x, n);
-    SVI_LAUNCH_CHECK();
-    return SVI_OK;
-}
-
 }  // namespace
 
-struct svi_w2v {
-    int device = -1;
+struct svi_w2v : EncHandle {
     svi_w2v_config cfg{};
-    std::map<std::string, Param> w;
-    char* ws = nullptr; size_t ws_bytes = 0;
     int max_frames = W2V_MAX_FRAMES;                 // svi_w2v_set_max_frames
 };
 
 namespace {
 
-bool w2v_expected(const svi_w2v_config& c, const std::string& name, std::vector<int64_t>* shape, bool* used) {
+const char* const W2V_CONV = "feature_extractor.conv_layers.";
+// Wav2Vec2Model's state dict with the positional convolution's weight norm folded (svi_hip.encoders.fold_weight_norm)
+void w2v_table(const svi_w2v_config& c, EncTable* t) {
     const int64_t C = c.conv_dim, H = c.hidden, F = c.ffn;
-    *used = true;
-    if (name == "masked_spec_embed") { *used = false; shape->clear(); return true; }             // training-time masking only
-    if (name.rfind("feature_extractor.conv_layers.", 0) == 0) {
-        char* end = nullptr;
-        const char* s = name.c_str() + 30;
-        const long i = strtol(s, &end, 10);
-        if (end == s || *end != '.' || i < 0 || i >= W2V_CONVS) return false;
-        const std::string rest(end + 1);
-        if (rest == "conv.weight") { *shape = {C, i == 0 ? 1 : C, W2V_KERNEL[i]}; return true; }
-        if (i == 0 && (rest == "layer_norm.weight" || rest == "layer_norm.bias")) { *shape = {C}; return true; }
-        return false;
-    }
-    if (name == "feature_projection.layer_norm.weight" || name == "feature_projection.layer_norm.bias") { *shape = {C}; return true; }
-    if (name == "feature_projection.projection.weight") { *shape = {H, C}; return true; }
-    if (name == "feature_projection.projection.bias") { *shape = {H}; return true; }
-    if (name == "encoder.pos_conv_embed.conv.weight") { *shape = {H, H / c.pos_groups, c.pos_kernel}; return true; }
-    if (name == "encoder.pos_conv_embed.conv.bias") { *shape = {H}; return true; }
-    if (name == "encoder.layer_norm.weight" || name == "encoder.layer_norm.bias") { *shape = {H}; return true; }
-    if (name.rfind("encoder.layers.", 0) != 0) return false;
-    char* end = nullptr;
-    const char* s = name.c_str() + 15;
-    const long i = strtol(s, &end, 10);
-    if (end == s || *end != '.' || i < 0 || i >= c.num_layers) return false;
-    const std::string rest(end + 1);
-    for (const char* p : {"attention.q_proj", "attention.k_proj", "attention.v_proj", "attention.out_proj"}) {
-        if (rest == std::string(p) + ".weight") { *shape = {H, H}; return true; }
-        if (rest == std::string(p) + ".bias") { *shape = {H}; return true; }
-    }
-    if (rest == "layer_norm.weight" || rest == "layer_norm.bias" || rest == "final_layer_norm.weight" || rest == "final_layer_norm.bias" ||
-        rest == "feed_forward.output_dense.bias") { *shape = {H}; return true; }
-    if (rest == "feed_forward.intermediate_dense.weight") { *shape = {F, H}; return true; }
-    if (rest == "feed_forward.intermediate_dense.bias") { *shape = {F}; return true; }
-    if (rest == "feed_forward.output_dense.weight") { *shape = {H, F}; return true; }
-    return false;
-}
-
-std::vector<std::string> w2v_keys(const svi_w2v_config& c) {
-    std::vector<std::string> k;
-    for (int i = 0; i < W2V_CONVS; ++i) k.push_back("feature_extractor.conv_layers." + std::to_string(i) + ".conv.weight");
-    for (const char* p : {"feature_extractor.conv_layers.0.layer_norm.weight", "feature_extractor.conv_layers.0.layer_norm.bias",
-                          "feature_projection.layer_norm.weight", "feature_projection.layer_norm.bias", "feature_projection.projection.weight",
-                          "feature_projection.projection.bias", "encoder.pos_conv_embed.conv.weight", "encoder.pos_conv_embed.conv.bias",
-                          "encoder.layer_norm.weight", "encoder.layer_norm.bias"})
-        k.push_back(p);
-    const char* per[] = {"attention.q_proj.weight", "attention.q_proj.bias", "attention.k_proj.weight", "attention.k_proj.bias",
-                         "attention.v_proj.weight", "attention.v_proj.bias", "attention.out_proj.weight", "attention.out_proj.bias",
-                         "layer_norm.weight", "layer_norm.bias", "feed_forward.intermediate_dense.weight", "feed_forward.intermediate_dense.bias",
-                         "feed_forward.output_dense.weight", "feed_forward.output_dense.bias", "final_layer_norm.weight", "final_layer_norm.bias"};
-    for (int i = 0; i < c.num_layers; ++i)
-        for (const char* p : per) k.push_back("encoder.layers." + std::to_string(i) + "." + p);
-    return k;
-}
-
-svi_status w2v_grow(svi_w2v* h, size_t need) {
-    if (h->ws_bytes >= need) return SVI_OK;
-    if (h->ws) { SVI_CHECK_HIP(hipFree(h->ws)); h->ws = nullptr; h->ws_bytes = 0; }       // hipFree waits for the work that still reads it
-    hipError_t e = hipMalloc((void**)&h->ws, need);
-    if (e != hipSuccess) { svi_set_error("hipMalloc(%zu B audio encoder workspace) failed: %s", need, hipGetErrorString(e)); return SVI_ERR_OOM; }
-    h->ws_bytes = need;
-    return SVI_OK;
+    t->noun = "audio encoder"; t->bind_fn = "svi_w2v_bind_weight"; t->max_rank = 3;
+    t->dtype = SVI_F32; t->dtype_words = "fp32 (the reference runs this model in fp32)";
+    t->layer_prefix = "encoder.layers."; t->layers = t->layers_used = c.num_layers;
+    for (int i = 0; i < W2V_CONVS; ++i) t->rows.push_back({W2V_CONV + std::to_string(i) + ".conv.weight", {C, i == 0 ? 1 : C, W2V_KERNEL[i]}, 0});
+    const EncRow rest[] = {{std::string(W2V_CONV) + "0.layer_norm.weight", {C}, 0}, {std::string(W2V_CONV) + "0.layer_norm.bias", {C}, 0},
+                           {"feature_projection.layer_norm.weight", {C}, 0}, {"feature_projection.layer_norm.bias", {C}, 0},
+                           {"feature_projection.projection.weight", {H, C}, 0}, {"feature_projection.projection.bias", {H}, 0},
+                           {"encoder.pos_conv_embed.conv.weight", {H, H / c.pos_groups, c.pos_kernel}, 0}, {"encoder.pos_conv_embed.conv.bias", {H}, 0},
+                           {"encoder.layer_norm.weight", {H}, 0}, {"encoder.layer_norm.bias", {H}, 0},
+                           {"masked_spec_embed", {}, ENC_UNUSED},                       // training-time masking only
+                           {"attention.q_proj.weight", {H, H}, ENC_LAYER}, {"attention.q_proj.bias", {H}, ENC_LAYER},
+                           {"attention.k_proj.weight", {H, H}, ENC_LAYER}, {"attention.k_proj.bias", {H}, ENC_LAYER},
+                           {"attention.v_proj.weight", {H, H}, ENC_LAYER}, {"attention.v_proj.bias", {H}, ENC_LAYER},
+                           {"attention.out_proj.weight", {H, H}, ENC_LAYER}, {"attention.out_proj.bias", {H}, ENC_LAYER},
+                           {"layer_norm.weight", {H}, ENC_LAYER}, {"layer_norm.bias", {H}, ENC_LAYER},
+                           {"feed_forward.intermediate_dense.weight", {F, H}, ENC_LAYER}, {"feed_forward.intermediate_dense.bias", {F}, ENC_LAYER},
+                           {"feed_forward.output_dense.weight", {H, F}, ENC_LAYER}, {"feed_forward.output_dense.bias", {H}, ENC_LAYER},
+                           {"final_layer_norm.weight", {H}, ENC_LAYER}, {"final_layer_norm.bias", {H}, ENC_LAYER}};
+    t->rows.insert(t->rows.end(), std::begin(rest), std::end(rest));
 }
 
 // what both entry points refuse before anything touches the device
@@ -482,26 +275,11 @@ svi_status w2v_run(svi_w2v* h, const float* samples, long n, int S, int stage, f
     long T[W2V_CONVS + 1];
     for (int i = 0; i <= W2V_CONVS; ++i) T[i] = w2v_frames_after(n, i);
     const long Tf = T[W2V_CONVS];
-    const int chunks_wave = (int)((n + ST_CHUNK - 1) / ST_CHUNK), chunks_gn = (int)((T[1] + ST_CHUNK - 1) / ST_CHUNK);
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t s_wave = al((size_t)n * 4), s_a = al((size_t)T[1] * C * 4), s_b = al((size_t)T[2] * C * 4);
-    const size_t s_part = al((size_t)std::max((size_t)chunks_wave, (size_t)chunks_gn * C) * 4), s_stat = al((size_t)2 * std::max(C, 1) * 4);
-    const size_t s_sc = al((size_t)S * C * 4), s_sh = al((size_t)S * H * 4), s_sf = al((size_t)S * std::max(F, 3 * H) * 4);
-    SVI_TRY(w2v_grow(h, s_wave + s_a + s_b + s_part + s_stat + 2 * s_sc + 4 * s_sh + s_sf));
-    char* p = h->ws;
-    float* Wv = reinterpret_cast<float*>(p); p += s_wave;
-    float* A = reinterpret_cast<float*>(p); p += s_a;
-    float* B = reinterpret_cast<float*>(p); p += s_b;
-    float* Part = reinterpret_cast<float*>(p); p += s_part;
-    float* Stat = reinterpret_cast<float*>(p); p += s_stat;
-    float* I0 = reinterpret_cast<float*>(p); p += s_sc;
-    float* I1 = reinterpret_cast<float*>(p); p += s_sc;
-    float* X = reinterpret_cast<float*>(p); p += s_sh;
-    float* Y = reinterpret_cast<float*>(p); p += s_sh;
-    float* N1 = reinterpret_cast<float*>(p); p += s_sh;
-    float* At = reinterpret_cast<float*>(p); p += s_sh;
-    float* Big = reinterpret_cast<float*>(p);                       // q | k | v, then the feed-forward's hidden rows
-    auto W = [&](const std::string& k) { return reinterpret_cast<const float*>(h->w[k].p); };
+    W2vBufs bufs;
+    SVI_TRY(svi_enc_carve(h, [&](EncArena& a) { bufs = w2v_buffers(a, n, T[1], T[2], ST_CHUNK, S, C, H, F); }));
+    float *const Wv = bufs.Wv, *const A = bufs.A, *const B = bufs.B, *const Part = bufs.Part, *const Stat = bufs.Stat, *const I0 = bufs.I0, *const I1 = bufs.I1,
+          *const X = bufs.X, *const Y = bufs.Y, *const N1 = bufs.N1, *const At = bufs.At, *const Big = bufs.Big;       // (not a structured binding: lambdas below capture them)
+#define W(k) SVI_ENC_W(float, h->w, k)
     // the tensor a stage names -> the caller's buffer; true: the forward ends here
     auto tap = [&](int which, const float* src, size_t count, bool* done) -> svi_status {
         *done = false;
@@ -536,7 +314,7 @@ svi_status w2v_run(svi_w2v* h, const float* samples, long n, int S, int stage, f
         float* dst = (i % 2 == 0) ? A : B;
         W2vConv a{};
         a.x = cur; a.Tin = T[i]; a.ldx = i == 0 ? 1 : C;
-        a.w = W("feature_extractor.conv_layers." + std::to_string(i) + ".conv.weight");
+        a.w = W(W2V_CONV + std::to_string(i) + ".conv.weight");
         a.y = dst; a.ldy = C; a.Tout = T[i + 1];
         a.Cin_g = i == 0 ? 1 : C; a.Cout_g = C; a.groups = 1; a.k = W2V_KERNEL[i]; a.s = W2V_STRIDE[i]; a.pad = 0;
         a.gelu = i == 0 ? 0 : 1;                                      // layer 0: GroupNorm comes between the convolution and the GELU
@@ -545,8 +323,7 @@ svi_status w2v_run(svi_w2v* h, const float* samples, long n, int S, int stage, f
             SVI_TRY(stats(dst, T[1], C));
             const long cnt = T[1] * C;
             hipLaunchKernelGGL(w2v_colnorm_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, (const float*)dst, dst, cnt, C, Stat, Stat + C,
-                               W2V_GROUPNORM_EPS, W("feature_extractor.conv_layers.0.layer_norm.weight"),
-                               W("feature_extractor.conv_layers.0.layer_norm.bias"), 1);
+                               W2V_GROUPNORM_EPS, W(std::string(W2V_CONV) + "0.layer_norm.weight"), W(std::string(W2V_CONV) + "0.layer_norm.bias"), 1);
             SVI_LAUNCH_CHECK();
         }
         SVI_TRY(tap(ST_CONV0 + i, dst, (size_t)T[i + 1] * C, &done));
@@ -590,7 +367,7 @@ svi_status w2v_run(svi_w2v* h, const float* samples, long n, int S, int stage, f
         SVI_TRY(svi_launch_gemm_f32(X, H, W(b + "attention.q_proj.weight"), H, W(b + "attention.q_proj.bias"), QKV, 3 * H, S, H, H, nullptr, 0, st));
         SVI_TRY(svi_launch_gemm_f32(X, H, W(b + "attention.k_proj.weight"), H, W(b + "attention.k_proj.bias"), QKV + H, 3 * H, S, H, H, nullptr, 0, st));
         SVI_TRY(svi_launch_gemm_f32(X, H, W(b + "attention.v_proj.weight"), H, W(b + "attention.v_proj.bias"), QKV + 2 * H, 3 * H, S, H, H, nullptr, 0, st));
-        SVI_TRY(svi_launch_enc_attention_f32(QKV, 3 * H, QKV + H, 3 * H, QKV + 2 * H, 3 * H, At, H, S, S, c.num_heads, D, scale, st));
+        SVI_TRY(svi_launch_enc_attention_f32(QKV, 3 * H, QKV + H, 3 * H, QKV + 2 * H, 3 * H, At, H, S, S, c.num_heads, D, scale, SVI_ENC_ATT_AUTO, st));
         SVI_TRY(svi_launch_gemm_f32(At, H, W(b + "attention.out_proj.weight"), H, W(b + "attention.out_proj.bias"), Y, H, S, H, H, X, H, st));
         SVI_TRY(svi_launch_layernorm_f32(Y, N1, W(b + "layer_norm.weight"), W(b + "layer_norm.bias"), S, H, c.eps, st));
         SVI_TRY(svi_launch_gemm_f32(N1, H, W(b + "feed_forward.intermediate_dense.weight"), H, W(b + "feed_forward.intermediate_dense.bias"), Big, F, S, F, H,
@@ -612,6 +389,7 @@ svi_status w2v_run(svi_w2v* h, const float* samples, long n, int S, int stage, f
     }
     SVI_REQUIRE(stage == ST_ALL, "svi_w2v_forward_stage: no stage %d (0 .. %d)", stage, ST_LAYER0 + c.num_layers - 1);
     return SVI_OK;
+#undef W
 }
 
 }  // namespace
@@ -624,10 +402,11 @@ extern "C" svi_status svi_w2v_create(const svi_w2v_config* cfg, svi_w2v** out) {
     SVI_REQUIRE(cfg->pos_kernel >= 1 && cfg->pos_kernel <= 128 && cfg->pos_groups >= 1 && cfg->hidden % cfg->pos_groups == 0,
                 "svi_w2v_create: positional convolution kernel %d (1..128) with %d groups over %d channels", cfg->pos_kernel, cfg->pos_groups, cfg->hidden);
     const int D = cfg->hidden / cfg->num_heads;
-    SVI_REQUIRE(D == 32 || D == 64 || D == 80 || D == 128, "svi_w2v_create: head dim %d (the encoder attention has 32, 64, 80, 128)", D);
+    SVI_REQUIRE(svi_enc_head_dim_ok(D), "svi_w2v_create: head dim %d (the encoder attention has 32, 64, 80, 128)", D);
     svi_w2v* h = new (std::nothrow) svi_w2v();
     if (!h) { svi_set_error("out of host memory"); return SVI_ERR_OOM; }
     h->cfg = *cfg;
+    w2v_table(*cfg, &h->w);
     *out = h;
     return SVI_OK;
 }
@@ -640,26 +419,13 @@ extern "C" svi_status svi_w2v_destroy(svi_w2v* h) {
 }
 
 extern "C" svi_status svi_w2v_bind_weight(svi_w2v* h, const char* name, const void* dev_ptr, svi_dtype dtype, const int64_t* shape, int32_t rank) {
-    SVI_REQUIRE(h && name && dev_ptr && shape && rank >= 1 && rank <= 3, "svi_w2v_bind_weight: bad argument");
-    SVI_REQUIRE(dtype == SVI_F32, "audio encoder parameter '%s' must be fp32 (the reference runs this model in fp32)", name);
-    SVI_REQUIRE(((uintptr_t)dev_ptr % 16) == 0, "audio encoder parameter '%s' is not 16-byte aligned", name);
-    std::vector<int64_t> want;
-    bool used = true;
-    if (!w2v_expected(h->cfg, name, &want, &used)) { svi_set_error("unknown audio encoder parameter '%s'", name); return SVI_ERR_INVALID; }
-    if (!used) return SVI_OK;
-    bool ok = (size_t)rank == want.size();
-    for (int i = 0; ok && i < rank; ++i) ok = shape[i] == want[i];
-    if (!ok) { svi_set_error("shape mismatch for audio encoder parameter '%s'", name); return SVI_ERR_INVALID; }
-    Param q; q.p = dev_ptr; q.shape = want;
-    h->w[name] = q;
-    return SVI_OK;
+    SVI_REQUIRE(h, "svi_w2v_bind_weight: bad argument");
+    return h->w.bind(name, dev_ptr, dtype, shape, rank);
 }
 
 extern "C" svi_status svi_w2v_check_bound(svi_w2v* h) {
     SVI_REQUIRE(h, "null handle");
-    for (const auto& k : w2v_keys(h->cfg))
-        if (!h->w.count(k)) { svi_set_error("audio encoder parameter '%s' was never bound", k.c_str()); return SVI_ERR_UNBOUND; }
-    return SVI_OK;
+    return h->w.check_bound();
 }
 
 extern "C" svi_status svi_w2v_set_max_frames(svi_w2v* h, int32_t max_frames) {
@@ -667,27 +433,6 @@ extern "C" svi_status svi_w2v_set_max_frames(svi_w2v* h, int32_t max_frames) {
     SVI_REQUIRE(max_frames >= 1 && max_frames <= W2V_FRAME_CAP, "svi_w2v_set_max_frames: max_frames %d (1 .. %d)", max_frames, W2V_FRAME_CAP);
     h->max_frames = max_frames;
     return SVI_OK;
-}
-
-extern "C" svi_status svi_encoder_attention_f32(const float* Q, int32_t ldq, const float* K, int32_t ldk, const float* V, int32_t ldv, float* O, int32_t ldo,
-                                                int32_t Lq, int32_t Lk, int32_t heads, int32_t D, float scale, int32_t kernel, svi_stream stream) {
-    SVI_REQUIRE(Q && K && V && O, "svi_encoder_attention_f32: null argument");
-    SVI_REQUIRE(D == 32 || D == 64 || D == 80 || D == 128, "svi_encoder_attention_f32: D %d (the encoder attention has 32, 64, 80, 128)", D);
-    SVI_REQUIRE(heads >= 1 && heads <= 65535 && Lq >= 1 && Lk >= 1, "svi_encoder_attention_f32: heads %d (1 .. 65535), Lq %d, Lk %d (at least 1)", heads, Lq, Lk);
-    SVI_REQUIRE(Lq <= W2V_FRAME_CAP, "svi_encoder_attention_f32: Lq %d is above the cap of %d rows", Lq, W2V_FRAME_CAP);
-    SVI_REQUIRE(Lk <= W2V_FRAME_CAP, "svi_encoder_attention_f32: Lk %d is above the cap of %d keys", Lk, W2V_FRAME_CAP);
-    const long row = (long)heads * D;
-    SVI_REQUIRE(ldq >= row, "svi_encoder_attention_f32: ldq %d is smaller than heads * D = %ld", ldq, row);
-    SVI_REQUIRE(ldk >= row, "svi_encoder_attention_f32: ldk %d is smaller than heads * D = %ld", ldk, row);
-    SVI_REQUIRE(ldv >= row, "svi_encoder_attention_f32: ldv %d is smaller than heads * D = %ld", ldv, row);
-    SVI_REQUIRE(ldo >= row, "svi_encoder_attention_f32: ldo %d is smaller than heads * D = %ld", ldo, row);
-    SVI_REQUIRE((((uintptr_t)Q | (uintptr_t)K | (uintptr_t)V | (uintptr_t)O) & 3) == 0, "svi_encoder_attention_f32: operands must be 4-byte aligned");
-    SVI_REQUIRE(kernel >= 0 && kernel <= 2, "svi_encoder_attention_f32: kernel %d (0: as the audio encoder launches, 1: resident, 2: streaming)", kernel);
-    SVI_REQUIRE(kernel != 1 || Lk <= W2V_MAX_FRAMES, "svi_encoder_attention_f32: kernel 1 (resident) holds at most 2048 keys, Lk is %d", Lk);
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (kernel == 2) return launch_enc_attention_stream(Q, ldq, K, ldk, V, ldv, O, ldo, Lq, Lk, heads, D, scale, st);
-    if (kernel == 1) return launch_enc_attention<float, false>(Q, ldq, K, ldk, V, ldv, O, ldo, Lq, Lk, heads, D, scale, nullptr, nullptr, 0, st);
-    return svi_launch_enc_attention_f32(Q, ldq, K, ldk, V, ldv, O, ldo, Lq, Lk, heads, D, scale, st);
 }
 
 extern "C" svi_status svi_w2v_frames(int64_t n_samples, int64_t* out) {

@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(os.path.dirname(HERE), "csrc")
 OBJ = os.path.join(CSRC, "obj")
 LIB = os.path.join(HERE, "libsvi_hip.so")
-SOURCES = ["svi_api.hip", "svi_elementwise.hip", "svi_gemm.hip", "svi_attention.hip", "svi_dit.hip", "svi_vae.hip", "svi_wav2vec.hip", "svi_lora.hip", "svi_pose_window.hip"]      # svi_wav2vec.hip includes svi_encoders.hip: one translation unit
+SOURCES = ["svi_api.hip", "svi_elementwise.hip", "svi_gemm.hip", "svi_attention.hip", "svi_dit.hip", "svi_vae.hip", "svi_encoder_kernels.hip", "svi_encoders.hip", "svi_wav2vec.hip", "svi_lora.hip", "svi_pose_window.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function"]
 
 
@@ -40,7 +40,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
     jobs = []
     for s in SOURCES:
         src, obj = os.path.join(CSRC, s), os.path.join(OBJ, s.replace(".hip", ".o"))
-        if force or _stale(obj, [src] + headers + ([os.path.join(CSRC, "svi_encoders.hip")] if s == "svi_wav2vec.hip" else [])):
+        if force or _stale(obj, [src] + headers):
             jobs.append((src, obj))
 
     def compile_one(job):

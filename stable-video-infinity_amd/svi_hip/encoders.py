@@ -26,27 +26,44 @@ def relative_position_buckets(num_buckets: int, max_dist: int, length: int) -> L
     return list(out)
 
 
-def _bind_all(fn, handle, state_dict: Dict[str, torch.Tensor], dtype: torch.dtype, code: int, keep: Dict[str, torch.Tensor], what: str) -> None:
-    for name, t in state_dict.items():
-        if not t.is_cuda or t.dtype != dtype or not t.is_contiguous():
-            raise RuntimeError(f"{what} parameter {name} must be a contiguous CUDA {dtype} tensor")
-        shape = (C.c_int64 * t.dim())(*t.shape)
-        L.check(fn(handle, name.encode(), t.data_ptr(), code, shape, t.dim()), f"bind {name}")
-        keep[name] = t
+class _Encoder:
+    """The handle of one native encoder: svi_<_ABI>_create / _bind_weight / _check_bound / _destroy, parameters of one dtype kept alive here."""
+    _ABI, _NOUN, _DTYPE, _CODE = "", "", torch.float32, L.SVI_F32
+
+    def _create(self, cfg) -> None:
+        h = C.c_void_p()
+        L.check(getattr(L.lib(), f"svi_{self._ABI}_create")(C.byref(cfg), C.byref(h)), f"svi_{self._ABI}_create")
+        self._h = h
+        self._params: Dict[str, torch.Tensor] = {}
+
+    def bind(self, state_dict: Dict[str, torch.Tensor]) -> None:
+        fn = getattr(L.lib(), f"svi_{self._ABI}_bind_weight")
+        for name, t in state_dict.items():
+            if not t.is_cuda or t.dtype != self._DTYPE or not t.is_contiguous():
+                raise RuntimeError(f"{self._NOUN} parameter {name} must be a contiguous CUDA {self._DTYPE} tensor")
+            shape = (C.c_int64 * t.dim())(*t.shape)
+            L.check(fn(self._h, name.encode(), t.data_ptr(), self._CODE, shape, t.dim()), f"bind {name}")
+            self._params[name] = t
+        L.check(getattr(L.lib(), f"svi_{self._ABI}_check_bound")(self._h), f"svi_{self._ABI}_check_bound")
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None):
+                getattr(L.lib(), f"svi_{self._ABI}_destroy")(self._h)
+                self._h = None
+        except Exception:
+            pass
 
 
-class WanTextEncoder:
+class WanTextEncoder(_Encoder):
     """Mirror of the reference class of the same name; parameters are bf16 and borrowed."""
+    _ABI, _NOUN, _DTYPE, _CODE = "t5", "text encoder", torch.bfloat16, L.SVI_BF16
 
     def __init__(self, vocab=256384, dim=4096, dim_attn=4096, dim_ffn=10240, num_heads=64, num_layers=24, num_buckets=32, shared_pos=False,
                  max_dist=128):
         self.vocab, self.dim, self.dim_attn, self.dim_ffn = vocab, dim, dim_attn, dim_ffn
         self.num_heads, self.num_layers, self.num_buckets, self.shared_pos = num_heads, num_layers, num_buckets, shared_pos
-        cfg = L.T5Config(vocab, dim, dim_attn, dim_ffn, num_heads, num_layers, num_buckets, max_dist, int(bool(shared_pos)))
-        h = C.c_void_p()
-        L.check(L.lib().svi_t5_create(C.byref(cfg), C.byref(h)), "svi_t5_create")
-        self._h = h
-        self._params: Dict[str, torch.Tensor] = {}
+        self._create(L.T5Config(vocab, dim, dim_attn, dim_ffn, num_heads, num_layers, num_buckets, max_dist, int(bool(shared_pos))))
 
     @classmethod
     def from_state_dict(cls, state_dict: Dict[str, torch.Tensor], device="cuda", **overrides) -> "WanTextEncoder":
@@ -66,10 +83,6 @@ class WanTextEncoder:
     def from_module(cls, module) -> "WanTextEncoder":
         """An existing reference WanTextEncoder on the GPU in bf16: parameters are borrowed in place."""
         return cls.from_state_dict(dict(module.state_dict()))
-
-    def bind(self, state_dict: Dict[str, torch.Tensor]) -> None:
-        _bind_all(L.lib().svi_t5_bind_weight, self._h, state_dict, torch.bfloat16, L.SVI_BF16, self._params, "text encoder")
-        L.check(L.lib().svi_t5_check_bound(self._h), "svi_t5_check_bound")
 
     def forward(self, ids: torch.Tensor, mask: Optional[torch.Tensor] = None, rows: str = "all") -> torch.Tensor:
         """ids [B, L] integer, mask [B, L] (tokenizer padding: a prefix of ones) -> [B, L, dim] bf16.
@@ -99,26 +112,15 @@ class WanTextEncoder:
 
     __call__ = forward
 
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                L.lib().svi_t5_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
 
-
-class WanImageEncoder:
+class WanImageEncoder(_Encoder):
     """Mirror of the reference class of the same name (the visual tower of open-clip XLM-R ViT-H/14, all but the last block)."""
+    _ABI, _NOUN = "clip", "image encoder"
 
     def __init__(self, image_size=224, patch_size=14, dim=1280, mlp_ratio=4, num_heads=16, num_layers=32, layers_used=None, norm_eps=1e-5):
         self.image_size, self.patch_size, self.dim, self.num_heads, self.num_layers = image_size, patch_size, dim, num_heads, num_layers
         used = num_layers - 1 if layers_used is None else layers_used                      # use_31_block=True (image_encoder:877)
-        cfg = L.ClipConfig(image_size, patch_size, dim, mlp_ratio, num_heads, num_layers, used, norm_eps)
-        h = C.c_void_p()
-        L.check(L.lib().svi_clip_create(C.byref(cfg), C.byref(h)), "svi_clip_create")
-        self._h = h
-        self._params: Dict[str, torch.Tensor] = {}
+        self._create(L.ClipConfig(image_size, patch_size, dim, mlp_ratio, num_heads, num_layers, used, norm_eps))
         self.tokens = (image_size // patch_size) ** 2 + 1
 
     @classmethod
@@ -150,10 +152,6 @@ class WanImageEncoder:
         vis = module.model.visual
         return cls.from_state_dict(dict(vis.state_dict()), num_heads=vis.num_heads, norm_eps=vis.norm_eps, **cfg)
 
-    def bind(self, state_dict: Dict[str, torch.Tensor]) -> None:
-        _bind_all(L.lib().svi_clip_bind_weight, self._h, state_dict, torch.float32, L.SVI_F32, self._params, "image encoder")
-        L.check(L.lib().svi_clip_check_bound(self._h), "svi_clip_check_bound")
-
     def encode_image(self, videos: Iterable[torch.Tensor]) -> torch.Tensor:
         """videos: list of [b, 3, H, W] tensors in [-1, 1] -> fp32 [sum b, tokens, dim] (hidden states after the last-but-one block)."""
         outs = []
@@ -167,20 +165,12 @@ class WanImageEncoder:
             outs.append(out)
         return torch.cat(outs) if len(outs) != 1 else outs[0]
 
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                L.lib().svi_clip_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
-
 
 W2V_CONV_KERNEL, W2V_CONV_STRIDE = (10, 3, 3, 3, 3, 2, 2), (5, 2, 2, 2, 2, 2, 2)
 W2V_STAGES = dict(wave=0, interp=8, proj=9, pos=10, enc_ln=11)          # conv layer i: 1 + i; block l: 12 + l (svi_w2v_forward_stage)
 _W2V_POS = "encoder.pos_conv_embed.conv."
 W2V_DEFAULT_MAX_FRAMES = 2048            # a fresh handle's frame limit: the resident encoder attention's key count, about 81 s of audio
-W2V_FRAME_CAP = 65536                    # W2V_FRAME_CAP of csrc/svi_wav2vec.hip: the most max_frames can be (43.7 min at 25 frames per second)
+W2V_FRAME_CAP = 65536                    # W2V_FRAME_CAP of csrc/svi_wav2vec.hip (= SVI_ENC_MAX_KEYS, csrc/svi_common.h): the most max_frames can be (43.7 min at 25 frames per second)
 
 
 def audio_frames(n_samples: int) -> int:
@@ -209,7 +199,7 @@ def fold_weight_norm(state_dict: Dict[str, torch.Tensor]) -> Dict[str, torch.Ten
     return sd
 
 
-class WanAudioEncoder:
+class WanAudioEncoder(_Encoder):
     """The talk variant's audio encoder on the device: wav2vec2-base as utils/audio_process.py:18-41 get_embedding runs it
     (utils/src/audio_analysis/wav2vec2.py Wav2Vec2Model.forward with seq_len and output_hidden_states=True), fp32; parameters are fp32 copies
     owned here.  The input is the ALREADY loudness-normalised 16 kHz mono array: loudness normalisation (pyloudnorm) and reading wav / mp4 files
@@ -220,15 +210,12 @@ class WanAudioEncoder:
     2048 frames do not depend on it, bit for bit."""
 
     FRAME_CAP = W2V_FRAME_CAP
+    _ABI, _NOUN = "w2v", "audio encoder"
 
     def __init__(self, conv_dim=512, hidden=768, ffn=3072, num_heads=12, num_layers=12, pos_kernel=128, pos_groups=16, eps=1e-5, max_frames=None):
         self.conv_dim, self.hidden, self.ffn, self.num_heads, self.num_layers = conv_dim, hidden, ffn, num_heads, num_layers
         self.pos_kernel, self.pos_groups, self.eps = pos_kernel, pos_groups, eps
-        cfg = L.W2vConfig(conv_dim, hidden, ffn, num_heads, num_layers, pos_kernel, pos_groups, eps)
-        h = C.c_void_p()
-        L.check(L.lib().svi_w2v_create(C.byref(cfg), C.byref(h)), "svi_w2v_create")
-        self._h = h
-        self._params: Dict[str, torch.Tensor] = {}
+        self._create(L.W2vConfig(conv_dim, hidden, ffn, num_heads, num_layers, pos_kernel, pos_groups, eps))
         self._max_frames = W2V_DEFAULT_MAX_FRAMES
         if max_frames is not None:
             self.max_frames = max_frames
@@ -277,10 +264,6 @@ class WanAudioEncoder:
     def from_module(cls, hf_model, device="cuda", max_frames=None) -> "WanAudioEncoder":
         """An existing (reference) Wav2Vec2Model: its parameters are copied to fp32 tensors on the device."""
         return cls.from_state_dict(dict(hf_model.state_dict()), hf_model.config, device=device, max_frames=max_frames)
-
-    def bind(self, state_dict: Dict[str, torch.Tensor]) -> None:
-        _bind_all(L.lib().svi_w2v_bind_weight, self._h, state_dict, torch.float32, L.SVI_F32, self._params, "audio encoder")
-        L.check(L.lib().svi_w2v_check_bound(self._h), "svi_w2v_check_bound")
 
     @staticmethod
     def _samples(speech) -> torch.Tensor:
@@ -332,11 +315,3 @@ class WanAudioEncoder:
         out = torch.empty(shape, dtype=torch.float32, device=x.device)
         L.check(L.lib().svi_w2v_forward_stage(self._h, L.ptr(x), n, S, code, L.ptr(out), out.numel(), L.current_stream()), "svi_w2v_forward_stage")
         return out
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                L.lib().svi_w2v_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass

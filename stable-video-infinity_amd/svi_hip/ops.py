@@ -194,7 +194,7 @@ def audio_windows(emb: torch.Tensor, start: int, T_latent: int):
 
 ENCODER_ATTENTION_KERNELS = {"auto": 0, "resident": 1, "streaming": 2}
 ENCODER_ATTENTION_RESIDENT_KEYS = 2048      # the resident kernel's key count (whole score rows in LDS)
-ENCODER_ATTENTION_KEY_TILE = 256            # ENC_KT of csrc/svi_wav2vec.hip: keys per tile of the streaming kernel
+ENCODER_ATTENTION_KEY_TILE = 256            # ENC_KT of csrc/svi_encoder_kernels.hip: keys per tile of the streaming kernel
 ENCODER_ATTENTION_MAX_KEYS = 65536          # W2V_FRAME_CAP of csrc/svi_wav2vec.hip: what svi_w2v_set_max_frames grants at most
 
 

@@ -156,7 +156,8 @@ def test_the_python_constants_are_the_sources():
     from svi_hip.encoders import W2V_DEFAULT_MAX_FRAMES, W2V_FRAME_CAP
     csrc = os.path.join(ROOT, "stable-video-infinity_amd", "csrc")
     w2v = open(os.path.join(csrc, "svi_wav2vec.hip")).read()
-    assert int(re.search(r"#define ENC_KT (\d+)", w2v).group(1)) == ops.ENCODER_ATTENTION_KEY_TILE
+    kernels = open(os.path.join(csrc, "svi_encoder_kernels.hip")).read()
+    assert int(re.search(r"#define ENC_KT (\d+)", kernels).group(1)) == ops.ENCODER_ATTENTION_KEY_TILE
     assert int(re.search(r"constexpr int W2V_FRAME_CAP = (\d+);", w2v).group(1)) == W2V_FRAME_CAP
     assert int(re.search(r"constexpr int W2V_MAX_FRAMES = (\d+);", w2v).group(1)) == W2V_DEFAULT_MAX_FRAMES
 

@@ -14,7 +14,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRCS = ["svi_attention.hip", "svi_gemm.hip", "svi_dit.hip", "svi_elementwise.hip", "svi_vae.hip", "svi_api.hip", "svi_encoders.hip",
-        "svi_lora.hip", "svi_common.h", "svi_fp8.h"]          # the shared device code (MFMA fragment helpers, the MX quantiser, GELU) is part of every kernel: gated too
+        "svi_encoder_kernels.hip", "svi_wav2vec.hip", "svi_encoder_host.h", "svi_lora.hip", "svi_common.h", "svi_fp8.h"]          # the shared device code (MFMA fragment helpers, the MX quantiser, GELU) is part of every kernel: gated too
 
 
 def source_hashes():
